@@ -19,7 +19,7 @@ EXPORTED_SYMBOLS = [
     "abm_map_se_batch", "abm_map_se_batch_sliced", "abm_ctx_slice_results", "abm_map_se_device", "abm_map_pe_batch", "abm_map_pe_device",
     "abm_max_read_length", "abm_ctx_reads_too_long", "abm_ctx_filter_on_planes", "abm_ctx_long_cigars", "abm_ctx_take_work", "abm_ctx_set_phase_stamps", "abm_ctx_set_read_cycles", "abm_ctx_set_timing", "abm_ctx_take_kernel_time", "abm_ctx_take_kernel_times", "abm_ctx_take_work_tiers", "abm_stats_allreduce",
     "abm_device_count", "abm_host_alloc", "abm_host_free", "abm_index_set_seed_extension", "abm_index_set_max_candidates", "abm_index_set_direct_narrowing", "abm_ctx_seed_extension", "abm_ctx_rebuild_seed_extension", "abm_device_numa_node",
-    "abm_ctx_set_pe_split", "abm_ctx_pe_split_stats", "abm_ctx_pe_timed_launches", "abm_ctx_set_pair_phases", "abm_device_memory", "abm_ctx_pe_footprint", "abm_index_set_seed_extension_cap", "abm_ctx_pinned_bytes", "abm_ctx_set_sam_tails", "abm_ctx_slice_sam_tails",
+    "abm_ctx_set_pe_split", "abm_ctx_pe_split_stats", "abm_ctx_pe_timed_launches", "abm_ctx_set_pair_phases", "abm_device_memory", "abm_ctx_pe_footprint", "abm_index_set_seed_extension_cap", "abm_ctx_pinned_bytes", "abm_ctx_set_sam_tails", "abm_ctx_slice_sam_tails", "abm_ctx_pe_sam_tails",
     "abm_index_set_window_records", "abm_ctx_window_records",
 ]
 
@@ -288,8 +288,36 @@ class Context:
         _check(self._lib.abm_map_se_device(self.handle, mode, C.byref(params), n, d_blob, d_off, max_len,
                                            d_res, d_cig, cig_stride, d_cig_n, d_status, stream))
 
-    def map_pe(self, reads1, reads2, mode=PE_NORMAL, params=None):
-        """abm_map_pe_batch.  Returns (pairs, se1, se2, (cig1, off1), (cig2, off2))."""
+    def set_sam_tails(self, on=True, allow_ambig=False):
+        """abm_ctx_set_sam_tails: the kernels write SAM records after QNAME (map_pe(sam=True) returns them)"""
+        _check(self._lib.abm_ctx_set_sam_tails(self.handle, 1 if on else 0, 1 if allow_ambig else 0))
+
+    def pinned_bytes(self):
+        self._lib.abm_ctx_pinned_bytes.argtypes = [C.c_void_p]
+        self._lib.abm_ctx_pinned_bytes.restype = C.c_uint64
+        return int(self._lib.abm_ctx_pinned_bytes(self.handle))
+
+    def pe_sam_tails(self, n):
+        """abm_ctx_pe_sam_tails for pairs [0, n) of the last batch: (kinds[u8], tails as [(bytes end 1, bytes end 2)]),
+        or (None, None) when the batch wrote no text"""
+        tails, stride = C.c_void_p(), C.c_uint32()
+        lens, kinds = C.c_void_p(), C.c_void_p()
+        self._lib.abm_ctx_pe_sam_tails.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _check(self._lib.abm_ctx_pe_sam_tails(self.handle, 0, n, C.byref(tails), C.byref(stride), C.byref(lens), C.byref(kinds)))
+        if not tails.value:
+            return None, None
+        st = int(stride.value)
+        k = np.ctypeslib.as_array(C.cast(kinds.value, C.POINTER(C.c_uint8)), shape=(max(n, 1),))[:n].copy()
+        ln = np.ctypeslib.as_array(C.cast(lens.value, C.POINTER(C.c_uint32)), shape=(max(2 * n, 1),))[: 2 * n].copy()
+        raw = C.string_at(tails.value, 2 * n * st) if n else b""
+        out = [(raw[(2 * i) * st:(2 * i) * st + int(ln[2 * i])], raw[(2 * i + 1) * st:(2 * i + 1) * st + int(ln[2 * i + 1])])
+               for i in range(n)]
+        return k, out
+
+    def map_pe(self, reads1, reads2, mode=PE_NORMAL, params=None, sam=False):
+        """abm_map_pe_batch.  Returns (pairs, se1, se2, (cig1, off1), (cig2, off2)); with sam=True (after
+        set_sam_tails) also the per-pair kinds (0 pair records, 1 single-end records, 0xFF the host's) and both ends'
+        SAM records after QNAME as bytes: (..., kinds, tails) -- (None, None) if the batch wrote none."""
         params = params or Params()
         b1, o1 = blob_and_offsets(reads1)
         b2, o2 = blob_and_offsets(reads2)
@@ -309,7 +337,10 @@ class Context:
                                           b2.ctypes.data, o2.ctypes.data, pairs.ctypes.data, se1.ctypes.data,
                                           se2.ctypes.data, c1.ctypes.data, co1.ctypes.data, c2.ctypes.data,
                                           co2.ctypes.data, cap))
-        return pairs, se1, se2, (c1[: int(co1[-1])], co1), (c2[: int(co2[-1])], co2)
+        out = (pairs, se1, se2, (c1[: int(co1[-1])], co1), (c2[: int(co2[-1])], co2))
+        if sam:
+            out = out + self.pe_sam_tails(n)
+        return out
 
     def reads_too_long(self):
         return int(self._lib.abm_ctx_reads_too_long(self.handle))

@@ -190,6 +190,10 @@ struct abm_ctx {
   uint32_t sam_stride = 0;          // of the launch whose results the buffers hold
   HostBuf<char> h_sam;
   HostBuf<abm::u32> h_sam_len;
+  // ... and by the pair kernels (abm_map_pe_batch): both ends' lines in h_sam, their lengths in h_sam_len, a kind per pair
+  uint32_t pe_sam_stride = 0;       // of the paired-end batch whose results the buffers hold (0: none written)
+  uint64_t pe_sam_pairs = 0;
+  HostBuf<abm::u8> h_pe_kind;
   HostBuf<abm_hit> h_res;           // hits on their way out (a pinned target keeps the copy on the DMA engines)
   HostBuf<abm_hit> h_pe_out;        // paired-end results (pairs, then both fallback hits) written by the kernels, pinned
   unsigned launch_seq = 0;
@@ -323,6 +327,8 @@ abm::u32 sam_stride_for(const abm_ctx *ctx, abm::u32 eff_len, abm::u32 cig_strid
   for (const std::string &nm : ctx->ix->h.chrom_names) longest_name = std::max(longest_name, nm.size());
   return static_cast<abm::u32>((eff_len + longest_name + 64 + 12 * static_cast<size_t>(std::min<abm::u32>(cig_stride, 8)) + 15) & ~static_cast<size_t>(15));
 }
+// the same for one end of a pair: RNEXT "=", PNEXT and TLEN (up to 10 digits and a sign) in the place of "*\t0\t0"
+abm::u32 pe_sam_stride_for(const abm_ctx *ctx, abm::u32 eff_len, abm::u32 cig_stride) { return sam_stride_for(ctx, eff_len, cig_stride) + 32; }
 abm::u32 bitwords_for(abm::u32 max_len) { return (max_len + 63) / 64 + 1; }
 
 void check_params(const abm_params *p) {
@@ -501,9 +507,11 @@ void se_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
   a.blob = d_blob;
   a.off = reinterpret_cast<const abm::u64 *>(d_off);
   ctx->sam_stride = 0;
-  if (ctx->sam_on && ctx->host_results && sliced) {
+  ctx->pe_sam_stride = 0;  // (the buffers are shared with the paired-end text)
+  if (ctx->sam_on && ctx->host_results && sliced && sam_stride_for(ctx, eff_len, cig_stride) <= abm::sam_line_room(a.GW, a.tb_extra)) {
     // the kernel writes every read's SAM text (after QNAME) next to its hit; a line that does not fit its slot is formatted
-    // by the host as before
+    // by the host as before.  (A slot longer than the LDS the line is built in -- very long chromosome names -- and the
+    // launch writes no text.)
     const abm::u32 stride = sam_stride_for(ctx, eff_len, cig_stride);
     ctx->h_sam.reserve(static_cast<size_t>(n) * stride);
     ctx->h_sam_len.reserve(n);
@@ -744,6 +752,33 @@ void pe_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
   a.allow_ambig = params->allow_ambig;
   a.pairs = reinterpret_cast<abm::Hit *>(d_pair);
   a.se1 = reinterpret_cast<abm::Hit *>(d_se1); a.se2 = reinterpret_cast<abm::Hit *>(d_se2);
+  // SAM text (abm_ctx_set_sam_tails): the launches that finish pairs write both ends' records after QNAME into pinned
+  // memory (format_pe_tails).  Their builds on the bit planes only, not the diagnostic ones, and only if a line's slot
+  // fits the LDS it is built in; otherwise the batch has no text and the host formats it all.
+  ctx->sam_stride = 0;
+  ctx->pe_sam_stride = 0;
+  bool text = false;
+  if (ctx->sam_on && ctx->host_results && !ctx->phase_stamps && a.G != 0) {
+    const abm::u32 stride = pe_sam_stride_for(ctx, eff_len, cig_stride);
+    if (stride <= abm::sam_line_room(a.GW, a.tb_extra)) {
+      ctx->h_sam.reserve(static_cast<size_t>(2 * n) * stride);
+      ctx->h_sam_len.reserve(2 * n);
+      ctx->h_pe_kind.reserve(n);
+      std::memset(ctx->h_pe_kind.p, abm::kPeTextHost, n);  // (a pair no launch finished stays the host's)
+      std::memset(ctx->h_sam_len.p, 0, 2 * n * sizeof(abm::u32));
+      a.blob1 = d_blob1; a.off1 = reinterpret_cast<const abm::u64 *>(d_off1);
+      a.blob2 = d_blob2; a.off2 = reinterpret_cast<const abm::u64 *>(d_off2);
+      a.sam_tail = ctx->h_sam.p;
+      a.sam_len = ctx->h_sam_len.p;
+      a.sam_kind = ctx->h_pe_kind.p;
+      a.sam_stride = stride;
+      a.sam_allow_ambig = ctx->sam_allow_ambig;
+      ctx->pe_sam_stride = stride;
+      ctx->pe_sam_pairs = n;
+      text = true;
+    }
+  }
+  const size_t fin_lds = text ? abm::kPeFinBytes : 0;
   a.cig1 = d_cig1; a.cig2 = d_cig2; a.cig_stride = cig_stride; a.cig_n1 = d_cig_n1; a.cig_n2 = d_cig_n2;
   a.ctmp_cap = eff_len + 2;
   const bool has_long = max_len > abm::kLdsReadLen;
@@ -777,12 +812,13 @@ void pe_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
   bool split = ctx->pe_split != 0;  // (0: tier 1 as ONE kernel per pair, as in rounds 1-4 -- same-box comparisons)
   if (const char *e = experiment_env("ABM_PE_SPLIT")) split = e[0] != '0';
   const size_t events_before = ctx->events_used;
-  const size_t lds1 = abm::pe_lds_bytes(W, WB, a.GW, a.ctmp_cap, eff_len, size_frac, abm::kPeTier1Cap, false);
+  const size_t lds1 = abm::pe_lds_bytes(W, WB, a.GW, a.ctmp_cap, eff_len, size_frac, abm::kPeTier1Cap, false) + fin_lds;
   if (!split) {
     // tier 1 unsplit: every pair, seeding and mating in one kernel, small sets in LDS
     a.cap = abm::kPeTier1Cap;
     int wps = abm::pe_waves_per_simd(lds1, ctx->phase_stamps, a.G != 0);
     if (const char *e = experiment_env("ABM_PE_WPS")) { if (!ctx->phase_stamps && a.G != 0 && (e[0] == '3' || e[0] == '4')) wps = e[0] - '0'; }
+    if (text) wps = abm::pe_text_waves_per_simd();  // (the text builds: launch_map_pe)
     const int waves = abm::pe_resident_waves(lds1, false, wps);
     if (waves <= 0) throw HipFail("map_pe_kernel (tier 1) does not fit on this device");
     ctx->payload1.reserve(static_cast<size_t>(waves) * a.cap);
@@ -792,7 +828,7 @@ void pe_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
     HIPCHK(hipMemsetAsync(counter, 0, sizeof(unsigned long long), st));
     a.next_read = counter;
     const hipEvent_t e1 = begin_timed(ctx, st);
-    HIPCHK(abm::launch_map_pe(a, lds1, static_cast<abm::u32>(std::min<uint64_t>(n, waves)), false, ctx->phase_stamps, wps, st));
+    HIPCHK(abm::launch_map_pe(a, lds1, static_cast<abm::u32>(std::min<uint64_t>(n, waves)), false, ctx->phase_stamps, wps, st, text));
     if (e1) HIPCHK(hipEventRecord(e1, st));
   }
   else {
@@ -840,7 +876,7 @@ void pe_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
     // MATE, small lists (every list of the pair within kPeTier1Cap entries: LDS): sort, scoring, mating, tracebacks,
     // best_single, fallback -- instruction-bound, it overlaps with the other contexts' seed kernels
     {
-      const size_t lds_m = abm::pe_mate_lds_bytes(W, a.GW, a.ctmp_cap, eff_len, size_frac, a.cap, false);
+      const size_t lds_m = abm::pe_mate_lds_bytes(W, a.GW, a.ctmp_cap, eff_len, size_frac, a.cap, false) + fin_lds;
       const int waves_m = abm::pe_mate_resident_waves(lds_m, false);
       if (waves_m <= 0) throw HipFail("map_pe_kernel (mate) does not fit on this device");
       a.order = nullptr;  // (in input order: the lists were handed over in whatever order the seed kernel finished them)
@@ -848,7 +884,7 @@ void pe_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
       HIPCHK(hipMemsetAsync(counter, 0, sizeof(unsigned long long), st));
       a.next_read = counter;
       const hipEvent_t e1 = begin_timed(ctx, st);
-      HIPCHK(abm::launch_pe_mate(a, lds_m, static_cast<abm::u32>(std::min<uint64_t>(n, waves_m)), false, ctx->phase_stamps, st));
+      HIPCHK(abm::launch_pe_mate(a, lds_m, static_cast<abm::u32>(std::min<uint64_t>(n, waves_m)), false, ctx->phase_stamps, st, text));
       if (e1) HIPCHK(hipEventRecord(e1, st));
     }
   }
@@ -856,12 +892,13 @@ void pe_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
   {
     a.cap = abm::kPeCapLarge;
     a.order = nullptr;
-    const size_t lds = abm::pe_lds_bytes(W, WB, a.GW, a.ctmp_cap, eff_len, size_frac, a.cap, true);
+    const size_t lds = abm::pe_lds_bytes(W, WB, a.GW, a.ctmp_cap, eff_len, size_frac, a.cap, true) + fin_lds;
     int wps = abm::pe_waves_per_simd(lds, ctx->phase_stamps, a.G != 0);
     if (const char *e = experiment_env("ABM_PE_WPS2")) { if (!ctx->phase_stamps && a.G != 0 && (e[0] == '3' || e[0] == '4')) wps = e[0] - '0'; }
+    if (text) wps = abm::pe_text_waves_per_simd();  // (the text builds: launch_map_pe)
     int waves = abm::pe_resident_waves(lds, true, wps);
     if (waves <= 0) throw HipFail("map_pe_kernel (tier 2) does not fit on this device");
-    const size_t lds_mb = abm::pe_mate_lds_bytes(W, a.GW, a.ctmp_cap, eff_len, size_frac, a.cap, true);
+    const size_t lds_mb = abm::pe_mate_lds_bytes(W, a.GW, a.ctmp_cap, eff_len, size_frac, a.cap, true) + fin_lds;
     int waves_mb = split ? abm::pe_mate_resident_waves(lds_mb, true) : 0;
     if (split && waves_mb <= 0) throw HipFail("map_pe_kernel (mate, tier 2) does not fit on this device");
     // (no more waves than the batch has pairs: every wave owns 2.3 MB of lists, heap and log in global memory -- 7.6 GB for
@@ -884,7 +921,7 @@ void pe_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
       HIPCHK(hipMemsetAsync(counter, 0, sizeof(unsigned long long), st));
       a.next_read = counter;
       const hipEvent_t e1 = begin_timed(ctx, st);
-      HIPCHK(abm::launch_pe_mate(a, lds_mb, static_cast<abm::u32>(waves_mb), true, ctx->phase_stamps, st));
+      HIPCHK(abm::launch_pe_mate(a, lds_mb, static_cast<abm::u32>(waves_mb), true, ctx->phase_stamps, st, text));
       if (e1) HIPCHK(hipEventRecord(e1, st));
       a.subset = ctx->subset.p; a.subset_count = ctx->subset_count.p;
     }
@@ -899,7 +936,7 @@ void pe_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
       a.host_tail = ctx->h_tail.p;
     }
     const hipEvent_t e1 = begin_timed(ctx, st);
-    HIPCHK(abm::launch_map_pe(a, lds, static_cast<abm::u32>(waves), true, ctx->phase_stamps, wps, st));
+    HIPCHK(abm::launch_map_pe(a, lds, static_cast<abm::u32>(waves), true, ctx->phase_stamps, wps, st, text));
     if (e1) HIPCHK(hipEventRecord(e1, st));
     a.finished = nullptr;
     a.host_tail = nullptr;
@@ -1252,7 +1289,7 @@ void abm_ctx_destroy(abm_ctx *c) {
       c->rep->arena = nullptr;
     }
   }
-  c->packed.release(); c->packed2.release(); c->lens2.release(); c->subset.release(); c->subset_count.release(); c->payload1.release(); c->payload2.release(); c->list2.release(); c->heap2.release(); c->log2.release(); c->need_big.release(); c->hand_hdr.release(); c->hand_pos.release(); c->hand_d.release(); c->hand_count.release(); c->split_stats.release(); c->stage_pos.release(); c->stage_d.release(); c->subset_b.release(); c->subset_count_b.release(); c->class33_b.release(); c->pe_out.release(); c->cig2h.release(); c->cig_n2h.release(); c->blob2.release(); c->off2.release(); c->coff.release(); c->scan_tmp.release(); c->cblob.release(); c->lens.release(); c->long_list.release(); c->long_count.release(); c->long_ctmp.release(); c->packed_long.release(); c->packed_long2.release(); c->long_q.release(); c->long_tb.release(); c->order.release(); c->class33.release(); c->cls.release(); c->work.release(); c->next_read.release(); c->cig_arena.release(); c->cig_arena_count.release(); c->h_cn.release(); c->h_slots.release(); c->h_arena.release(); c->h_cn2.release(); c->h_slots2.release(); c->h_rel.release(); c->h_rel2.release(); c->h_res.release(); c->h_pe_out.release(); c->h_sam.release(); c->h_sam_len.release(); c->h_tail.release(); c->finished.release(); c->blob.release(); c->off.release();
+  c->packed.release(); c->packed2.release(); c->lens2.release(); c->subset.release(); c->subset_count.release(); c->payload1.release(); c->payload2.release(); c->list2.release(); c->heap2.release(); c->log2.release(); c->need_big.release(); c->hand_hdr.release(); c->hand_pos.release(); c->hand_d.release(); c->hand_count.release(); c->split_stats.release(); c->stage_pos.release(); c->stage_d.release(); c->subset_b.release(); c->subset_count_b.release(); c->class33_b.release(); c->pe_out.release(); c->cig2h.release(); c->cig_n2h.release(); c->blob2.release(); c->off2.release(); c->coff.release(); c->scan_tmp.release(); c->cblob.release(); c->lens.release(); c->long_list.release(); c->long_count.release(); c->long_ctmp.release(); c->packed_long.release(); c->packed_long2.release(); c->long_q.release(); c->long_tb.release(); c->order.release(); c->class33.release(); c->cls.release(); c->work.release(); c->next_read.release(); c->cig_arena.release(); c->cig_arena_count.release(); c->h_cn.release(); c->h_slots.release(); c->h_arena.release(); c->h_cn2.release(); c->h_slots2.release(); c->h_rel.release(); c->h_rel2.release(); c->h_res.release(); c->h_pe_out.release(); c->h_sam.release(); c->h_sam_len.release(); c->h_pe_kind.release(); c->h_tail.release(); c->finished.release(); c->blob.release(); c->off.release();
   c->res.release(); c->cig.release(); c->cig_n.release(); c->status.release();
   for (auto &e : c->events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   delete c;
@@ -1604,6 +1641,20 @@ int abm_ctx_slice_sam_tails(abm_ctx *ctx, uint64_t lo, uint64_t hi, const char *
   });
 }
 
+int abm_ctx_pe_sam_tails(abm_ctx *ctx, uint64_t lo, uint64_t hi, const char **tails, uint32_t *stride, const uint32_t **lens,
+                         const uint8_t **kinds) {
+  return guarded([&] {
+    if (!ctx || !tails || !stride || !lens || !kinds) throw std::invalid_argument("null argument");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->pe_sam_stride == 0) { *tails = nullptr; *lens = nullptr; *kinds = nullptr; *stride = 0; return; }
+    if (lo > hi || hi > ctx->pe_sam_pairs) throw std::invalid_argument("pair range outside the batch");
+    *tails = ctx->h_sam.p + 2 * lo * ctx->pe_sam_stride;
+    *lens = ctx->h_sam_len.p + 2 * lo;
+    *kinds = ctx->h_pe_kind.p + lo;
+    *stride = ctx->pe_sam_stride;
+  });
+}
+
 int abm_ctx_set_pe_split(abm_ctx *ctx, int split, uint32_t seed_cap, uint64_t hand_entries) {
   return guarded([&] {
     if (!ctx) throw std::invalid_argument("ctx is null");
@@ -1644,6 +1695,7 @@ uint64_t abm_ctx_pinned_bytes(const abm_ctx *c) {
   uint64_t b = 0;
   b += (c->h_cn.cap + c->h_slots.cap + c->h_arena.cap + c->h_cn2.cap + c->h_slots2.cap + c->h_tail.cap + c->h_slice_first.cap + c->h_slice_done.cap) * 4;
   b += (c->h_rel.cap + c->h_rel2.cap + c->h_res.cap + c->h_pe_out.cap) * 8;
+  b += c->h_sam.cap + c->h_sam_len.cap * 4 + c->h_pe_kind.cap;  // (SAM text)
   return b;
 }
 
@@ -1776,6 +1828,10 @@ int abm_ctx_reserve(abm_ctx *ctx, uint64_t n, uint32_t max_len, int paired) {
       else {
         ctx->blob2.reserve(n * L); ctx->off2.reserve(n + 1);
         ctx->packed2.reserve(n * 4 * W); ctx->lens2.reserve(n);
+        if (ctx->sam_on) {  // (what pe_device asks for with SAM text)
+          ctx->h_sam.reserve(2 * static_cast<size_t>(n) * pe_sam_stride_for(ctx, L, kPeHostSlotOps));
+          ctx->h_sam_len.reserve(2 * n); ctx->h_pe_kind.reserve(n);
+        }
         ctx->need_big.reserve(n); ctx->subset.reserve(n); ctx->subset_count.reserve(1);
         // (the phase split's hand-over area and second pair list, sized as pe_device sizes them for a batch of n pairs in the
         // random-PBAT mode's eight lists per pair: growing them mid-run frees the old ones, and hipFree waits for the whole

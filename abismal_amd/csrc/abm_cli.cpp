@@ -62,6 +62,15 @@ struct Stats {
 };
 struct Stats3 { Stats s[3]; };  // SE: s[0]; PE: pairs, read1, read2
 
+// paired input: the pair kernels write the SAM text when a GPU has fewer host workers than this to itself
+// (ABM_CLI_DEVICE_SAM=0 / 1 decides otherwise).  0 -- host formatting, the default as before -- until the threshold is
+// measured: what exists is 2 M pairs 2 x 150 on one GPU, ONE run per cell, all 24 contexts with text
+// (profiles/r06_pe_sam_text_e2e.log): mapping 1.42 -> 1.30 s at -t 2, 1.22 -> 1.32 s at -t 4, 1.28 -> 1.06 s at -t 16,
+// format busy 0.6 -> 0.2 s, the contexts' 17 GB of pinned slots 2-4 s more set-up and 4.6-6 s more process CPU, the
+// LDS-list mate kernel 90 -> 152 ms.  Not settled: medians over 8 M pairs, and runs with fewer text contexts per GPU
+// (ABM_CLI_PE_TEXT_CONTEXTS), are still to be taken.
+constexpr unsigned kPeDeviceSamWorkers = 0;
+std::atomic<uint64_t> g_device_records{0}, g_host_records{0};  // SAM / BAM records whose text the kernels / the formatters wrote
 // A batch's FASTQ text: grown with realloc (large blocks are remapped, not copied, and never
 // zero-filled) and recycled through a small pool so that its pages stay faulted in.
 std::atomic<uint64_t> g_pinned_bytes{0};  // page-locked memory the run has asked the library for (batches' read buffers)
@@ -186,6 +195,8 @@ struct Slice {
   bool has_tails = false;
   PodVec<uint32_t> tail_len;
   RawBuf tail_text;
+  // (pairs: two lengths per pair, end 1's then end 2's, and the pair's kind -- abm_ctx_pe_sam_tails; 0xFF = format it here)
+  PodVec<uint8_t> tail_kind;
 };
 
 // written slices are recycled with their buffers (names, reads, output text keep their capacity): a
@@ -1287,6 +1298,7 @@ int cmd_map(int argc, char **argv) {
   bool shared_device = false;
   for (int g = 0; g < n_gpus; ++g) for (int h = 0; h < g; ++h) shared_device |= dev_of[g] >= 0 && dev_of[g] == dev_of[h];
   bool device_sam = false;  // decided below, once the number of host workers is known
+  int pe_text_per_gpu = 0;  // paired: contexts per GPU whose batches carry SAM text from the device
   std::vector<abm_ctx *> ctxs;  // [g * per_gpu + k]
   if (!virtual_gpus) {
     // the first context on a device uploads the index and derives its tables there: every device's at the same time
@@ -1382,10 +1394,33 @@ int cmd_map(int argc, char **argv) {
       unsigned workers = opt.threads ? std::max(1u, opt.threads) : static_cast<unsigned>(std::min<size_t>(std::max<size_t>(topo.n_cores(), 1), 8u + 8u * static_cast<unsigned>(n_gpus)));
       if (q0.cpus > 0 && !std::getenv("ABM_CLI_NO_QUOTA_CLAMP")) workers = std::min(workers, std::max(1u, static_cast<unsigned>(q0.cpus + 0.5)));
       device_sam = !paired && !opt.bam && !std::getenv("ABM_CLI_NO_STREAM") && !std::getenv("ABM_CLI_HOST_FORMAT") && workers < 12u * static_cast<unsigned>(n_gpus);
-      if (const char *e = std::getenv("ABM_CLI_DEVICE_SAM")) device_sam = !paired && !opt.bam && !std::getenv("ABM_CLI_NO_STREAM") && e[0] != '0';
+      // paired SAM text: the pair kernels write both ends' records after QNAME (abm_ctx_pe_sam_tails).  Where it pays is
+      // taken from measurements on one GPU (kPeDeviceSamWorkers, below); the pinned slots it needs are bounded by
+      // pe_text_contexts.
+      if (paired) device_sam = !opt.bam && !std::getenv("ABM_CLI_HOST_FORMAT") && workers < kPeDeviceSamWorkers * static_cast<unsigned>(n_gpus);
+      if (const char *e = std::getenv("ABM_CLI_DEVICE_SAM")) device_sam = !opt.bam && (paired || !std::getenv("ABM_CLI_NO_STREAM")) && e[0] != '0';
+    }
+    if (device_sam && paired) {
+      // Pinned memory is what paired text costs: a context's slots hold a whole batch -- two lines of about read length +
+      // longest chromosome name + 200 bytes per pair (~700 B at 2x150), 0.7 GB per context of 1 M pairs, 17 GB for a GPU's
+      // 24.  Contexts get text while their slots fit half of the host's available memory, spread evenly over the GPUs;
+      // the others format on the host (the output is the same).
+      size_t longest_name = 0;
+      for (const std::string &nm : ch.names) longest_name = std::max(longest_name, nm.size());
+      const size_t batch_pairs = opt.batch ? opt.batch : env_reads("ABM_CLI_BATCH_READS", size_t(1) << 20);
+      const size_t per_ctx = batch_pairs * (2 * (std::max<size_t>(first_len, 48) + longest_name + 192) + 9);
+      const long pages = sysconf(_SC_AVPHYS_PAGES), page = sysconf(_SC_PAGESIZE);
+      const size_t avail = pages > 0 && page > 0 ? static_cast<size_t>(pages) * static_cast<size_t>(page) : 0;
+      const size_t fit = per_ctx ? (avail / 2) / per_ctx : 0;
+      pe_text_per_gpu = static_cast<int>(std::min<size_t>(static_cast<size_t>(per_gpu), fit / std::max(1, n_gpus)));
+      // (ABM_CLI_PE_TEXT_CONTEXTS=k: at most k text contexts per GPU -- an experiment / test knob, like ABM_CLI_DEVICE_SAM)
+      if (const char *e = std::getenv("ABM_CLI_PE_TEXT_CONTEXTS")) pe_text_per_gpu = std::min(per_gpu, std::max(0, std::atoi(e)));
+      if (pe_text_per_gpu == 0) device_sam = false;
     }
     if (device_sam)
-      for (abm_ctx *c : ctxs) if (abm_ctx_set_sam_tails(c, 1, opt.ambig ? 1 : 0) != 0) die_abm("SAM text on the device");
+      for (size_t c = 0; c < ctxs.size(); ++c)
+        if ((!paired || static_cast<int>(c % per_gpu) < pe_text_per_gpu) && abm_ctx_set_sam_tails(ctxs[c], 1, opt.ambig ? 1 : 0) != 0)
+          die_abm("SAM text on the device");
     std::vector<std::thread> warm;
     std::exception_ptr werr;
     std::mutex wmu;
@@ -2427,6 +2462,37 @@ int cmd_map(int argc, char **argv) {
               rc = abm_map_pe_batch(ctx, pe_mode, &par, n, blob_p[0], off_p[0], blob_p[1], off_p[1], b->pairs.data(),
                                     b->se[0].data(), b->se[1].data(), b->cig[0].data(), b->cig_off[0].data(),
                                     b->cig[1].data(), b->cig_off[1].data(), cap);
+              // the pair kernels' SAM text leaves the context's pinned slots before it maps again: each slice takes its
+              // pairs' kinds, lengths and text, compacted (as the single-end slice callback does)
+              for (auto &slp : b->slices) slp->has_tails = false;
+              if (rc == 0 && device_sam) {
+                const char *tails = nullptr; const uint32_t *lens = nullptr; const uint8_t *kinds = nullptr; uint32_t stride = 0;
+                if (abm_ctx_pe_sam_tails(ctx, 0, n, &tails, &stride, &lens, &kinds) != 0) die_abm("paired SAM text");
+                if (tails)
+                  for (auto &slp : b->slices) {
+                    Slice &sl = *slp;
+                    const size_t m = sl.n(), base = sl.base;
+                    sl.tail_kind.resize(std::max<size_t>(m, 1));
+                    sl.tail_len.resize(std::max<size_t>(2 * m, 1));
+                    // (a pair of kind 0xFF has no text: whatever its lengths say, none of it is taken -- the formatter
+                    // does not advance over it)
+                    size_t bytes = 0;
+                    for (size_t k = 0; k < m; ++k) {
+                      const bool text = kinds[base + k] != 0xFF;
+                      sl.tail_kind[k] = kinds[base + k];
+                      sl.tail_len[2 * k] = text ? lens[2 * (base + k)] : 0u;
+                      sl.tail_len[2 * k + 1] = text ? lens[2 * (base + k) + 1] : 0u;
+                      bytes += sl.tail_len[2 * k] + sl.tail_len[2 * k + 1];
+                    }
+                    sl.tail_text.clear();
+                    sl.tail_text.reserve(std::max<size_t>(bytes, 1));
+                    char *w = sl.tail_text.p;
+                    for (size_t j = 0; j < 2 * m; ++j)
+                      if (sl.tail_len[j]) { std::memcpy(w, tails + (2 * base + j) * stride, sl.tail_len[j]); w += sl.tail_len[j]; }
+                    sl.tail_text.n = static_cast<size_t>(w - sl.tail_text.p);
+                    sl.has_tails = true;
+                  }
+              }
             }
             if (rc == 0) break;
             if (rc == ABM_ERR_CAPACITY && cap < worst) { cap = worst; continue; }
@@ -2478,6 +2544,7 @@ int cmd_map(int argc, char **argv) {
     Stats3 &st = sl.stats;
     const size_t m = sl.n(), base = sl.base;
     sam.reserve(m * (paired ? 2 : 1) * 320);
+    uint64_t n_device_records = 0, n_host_records = 0;
     if (!paired) {
       // (a slice that took its own copy of the results indexes it by its own read numbers)
       const abm_hit *hits = sl.own ? sl.own_se.data() : b->se[0].data() + base;
@@ -2491,7 +2558,11 @@ int cmd_map(int argc, char **argv) {
         const size_t ncg = cig_off[k + 1] - cig_off[k];
         const uint32_t tl = sl.has_tails ? sl.tail_len[k] : 0xFFFFFFFFu;
         if (tl == 0xFFFFFFFFu) {  // (no text from the device for this read: format_se here)
-          if (len && emit_se(sam, opt.ambig, h, ch, sl.names[0][k], sl.blob[0].data() + sl.off[0][k], len, cg, ncg) == UNMAPPED) h.pos = 0;
+          if (len) {
+            const Outcome o = emit_se(sam, opt.ambig, h, ch, sl.names[0][k], sl.blob[0].data() + sl.off[0][k], len, cg, ncg);
+            if (o == UNMAPPED) h.pos = 0;
+            n_host_records += o == UNIQUE || (o == AMBIG && opt.ambig);
+          }
         }
         else if (len && (opt.ambig || !(h.flags & 0x100))) {
           // the kernel wrote the line after QNAME (or found no record: no hit, or one that runs across its chromosome's end)
@@ -2502,13 +2573,17 @@ int cmd_map(int argc, char **argv) {
             sam.resize(at0 + nm.n + tl);
             std::memcpy(&sam[at0], nm.p, nm.n);
             std::memcpy(&sam[at0 + nm.n], tail_at, tl);
+            ++n_device_records;
           }
         }
         if (tl != 0xFFFFFFFFu) tail_at += tl;
         st.s[0].tally(len == 0, h, opt.ambig, ref_len(cg, ncg));
       }
+      g_device_records += n_device_records;
+      g_host_records += n_host_records;
       return;
     }
+    const char *tail_at = sl.has_tails ? sl.tail_text.p : nullptr;
     for (size_t k = 0; k < m; ++k) {
       const size_t i = base + k;
       abm_pair p = b->pairs[i];
@@ -2517,14 +2592,41 @@ int cmd_map(int argc, char **argv) {
       const size_t l1 = sl.off[0][k + 1] - sl.off[0][k], l2 = sl.off[1][k + 1] - sl.off[1][k];
       const uint32_t *c1 = b->cig[0].data() + b->cig_off[0][i], *c2 = b->cig[1].data() + b->cig_off[1][i];
       const size_t nc1 = b->cig_off[0][i + 1] - b->cig_off[0][i], nc2 = b->cig_off[1][i + 1] - b->cig_off[1][i];
-      // select_output, src/abismal.cpp:1073-1088
-      const Outcome po = emit_pe(sam, opt.ambig, p, ch, sl.names[0][k], sl.names[1][k], s1, l1, s2, l2, c1, nc1, c2, nc2);
       const bool report = p.r1.pos != 0 && (opt.ambig || !(p.r1.flags & 0x100));
       bool pair_ok = report;
-      if (!report || po == UNMAPPED) {
-        if (po == UNMAPPED) { p.r1.pos = 0; p.r2.pos = 0; pair_ok = false; }
-        if (emit_se(sam, opt.ambig, h1, ch, sl.names[0][k], s1, l1, c1, nc1) == UNMAPPED) h1.pos = 0;
-        if (emit_se(sam, opt.ambig, h2, ch, sl.names[1][k], s2, l2, c2, nc2) == UNMAPPED) h2.pos = 0;
+      const uint8_t kind = sl.has_tails ? sl.tail_kind[k] : 0xFF;
+      if (kind == 0xFF) {
+        // select_output, src/abismal.cpp:1073-1088
+        const Outcome po = emit_pe(sam, opt.ambig, p, ch, sl.names[0][k], sl.names[1][k], s1, l1, s2, l2, c1, nc1, c2, nc2);
+        if (po != UNMAPPED && (opt.ambig || po != AMBIG)) n_host_records += 2;
+        if (!report || po == UNMAPPED) {
+          if (po == UNMAPPED) { p.r1.pos = 0; p.r2.pos = 0; pair_ok = false; }
+          const Outcome o1 = emit_se(sam, opt.ambig, h1, ch, sl.names[0][k], s1, l1, c1, nc1);
+          const Outcome o2 = emit_se(sam, opt.ambig, h2, ch, sl.names[1][k], s2, l2, c2, nc2);
+          if (o1 == UNMAPPED) h1.pos = 0;
+          if (o2 == UNMAPPED) h2.pos = 0;
+          n_host_records += (o1 != UNMAPPED && (opt.ambig || o1 != AMBIG)) + (o2 != UNMAPPED && (opt.ambig || o2 != AMBIG));
+        }
+      }
+      else {
+        // the kernel wrote the pair's records after QNAME (kind 0: the pair's; 1: single-end ones -- or none)
+        for (int e = 0; e < 2; ++e) {
+          const uint32_t tl = sl.tail_len[2 * k + e];
+          if (tl == 0) continue;
+          const NameRef &nm = sl.names[e][k];
+          const size_t at0 = sam.size();
+          sam.resize(at0 + nm.n + tl);
+          std::memcpy(&sam[at0], nm.p, nm.n);
+          std::memcpy(&sam[at0 + nm.n], tail_at, tl);
+          tail_at += tl;
+          ++n_device_records;
+        }
+        if (kind == 1) {
+          if (report) { p.r1.pos = 0; p.r2.pos = 0; pair_ok = false; }  // (unmapped as a pair: its ends on no one chromosome)
+          // an end without a record whose hit was not an ambiguous one left out: emit_se's UNMAPPED
+          if (sl.tail_len[2 * k] == 0 && (opt.ambig || !(h1.flags & 0x100))) h1.pos = 0;
+          if (sl.tail_len[2 * k + 1] == 0 && (opt.ambig || !(h2.flags & 0x100))) h2.pos = 0;
+        }
       }
       // paired_end_mapping_statistics::update, :1039-1057
       Stats &ps = st.s[0];
@@ -2537,6 +2639,8 @@ int cmd_map(int argc, char **argv) {
         st.s[2].tally(l2 == 0, h2, false, ref_len(c2, nc2));
       }
     }
+    g_device_records += n_device_records;
+    g_host_records += n_host_records;
   };
   // formats a slice; its place in its region's file is fixed once every earlier slice's size is known
   auto format_task = [&](Slice *sl) {
@@ -2751,7 +2855,7 @@ int cmd_map(int argc, char **argv) {
     std::ofstream tj(opt.timing);
     tj << "{\"records\": " << total_records << ", \"reads\": " << (paired ? 2 : 1) * total_records << ", \"seconds\": " << secs
        << ", \"index_load_s\": " << index_load_s << ", \"host_prepare_s\": " << host_prepare_s << ", \"gpus\": " << n_gpus << ", \"mappers_per_gpu\": " << per_gpu
-       << ", \"sam_text_by\": \"" << (device_sam ? "device" : "host") << "\", \"window_records_serve_reads_up_to\": " << (ctxs.empty() ? 0u : abm_ctx_window_records(ctxs[0])) << ", \"host_threads\": " << n_host << ", \"numa_nodes\": " << n_nodes << ", \"pinned\": " << (topo.pinning ? "true" : "false")
+       << ", \"sam_text_by\": \"" << (device_sam ? "device" : "host") << "\", \"sam_records\": {\"device\": " << g_device_records.load() << ", \"host\": " << g_host_records.load() << "}, \"pe_text_contexts_per_gpu\": " << (paired && device_sam ? pe_text_per_gpu : 0) << ", \"window_records_serve_reads_up_to\": " << (ctxs.empty() ? 0u : abm_ctx_window_records(ctxs[0])) << ", \"host_threads\": " << n_host << ", \"numa_nodes\": " << n_nodes << ", \"pinned\": " << (topo.pinning ? "true" : "false")
        << ", \"out_parts\": " << n_regions << ", \"out_bytes\": " << out_bytes << ", \"batches\": " << n_batches << ", \"max_lead_in_records\": " << max_lead << ", \"region_lead_in_scanned_records\": " << region_lead_scanned << ", \"region_lead_in_records\": " << region_lead_records
        << ", \"batch_reads\": " << batch_reads << ", \"host_ceiling\": " << (virtual_gpus ? "true" : "false")
        << ", \"batches_per_gpu\": [";

@@ -126,16 +126,37 @@ struct PeArgs {
   i16 *stage_d;                  // [grid][scap]
   u32 scap;
   unsigned long long *split_stats;  // optional [4]: pairs by route (small, whole, big), [3] unused
+  // optional: the pair's SAM records after QNAME written by the launch that finishes it (format_pe_tails; as
+  // SeArgs::sam_tail for single-end reads): the reads' text (blob / off of both ends: what the batch was packed from),
+  // the line of end e of pair r at sam_tail + (2 r + e) * sam_stride, its length in sam_len[2 r + e] (0 = no record),
+  // the pair's kind in sam_kind[r] (kPeText*).  Only the launches built with TEXT write them.
+  const char *blob1, *blob2;
+  const u64 *off1, *off2;
+  char *sam_tail;
+  u32 *sam_len;
+  u8 *sam_kind;
+  u32 sam_stride;
+  int sam_allow_ambig;
 };
 constexpr u8 kRouteSmall = 0, kRouteWhole = 1, kRouteBig = 2;
+// PeArgs::sam_kind: the pair's two records (format_pe), up to two single-end records (format_se: the fallback, or a pair
+// whose ends cannot both be located on one chromosome), or none written -- the host formats the whole pair
+constexpr u8 kPeTextPair = 0, kPeTextSingles = 1, kPeTextHost = 0xFF;
+// LDS a launch of the pair kernels with SAM text takes beyond its usual size: both ends' CigarSink::fin
+constexpr u32 kPeFinBytes = 2 * kSeCap * 4;
+// bytes of the LDS a SAM line is built in (the traceback table's place: window slots 1.., the window cache and the
+// table's extra bytes -- idle once the CIGARs are out), the same in the single-end and the pair kernels; a launch whose
+// text slot (sam_stride) is longer writes no text
+size_t sam_line_room(u32 GW, u32 tb_extra);
 
 // bytes the traceback table needs beyond the LDS it overlays (genome-window slots 1.. and the
 // window cache, both idle while a traceback runs); the kernels carve exactly this much extra
 u32 tb_extra_bytes(u32 GW, u32 max_len, double valid_frac);
 size_t pe_lds_bytes(u32 W, u32 WB, u32 GW, u32 cig_stride, u32 max_len, double valid_frac, u32 cap, bool big);
 int pe_waves_per_simd(size_t lds, bool timed, bool coop);  // which build of the pair kernels a launch with this much LDS per wave takes
+int pe_text_waves_per_simd();  // ... and the one the launches with SAM text take (launch_map_pe)
 int pe_resident_waves(size_t lds, bool big, int wps);
-hipError_t launch_map_pe(const PeArgs &a, size_t lds, u32 grid, bool big, bool timed, int wps, hipStream_t st);
+hipError_t launch_map_pe(const PeArgs &a, size_t lds, u32 grid, bool big, bool timed, int wps, hipStream_t st, bool text = false);
 hipError_t launch_collect_long_pairs(const u32 *d_lens1, const u32 *d_lens2, u64 n, u32 *d_list, u32 *d_count, hipStream_t st);
 size_t pe_long_lds_bytes(u32 GW);
 size_t pe_long_q_words(u32 W, u32 WB);
@@ -150,7 +171,7 @@ size_t pe_mate_lds_bytes(u32 W, u32 GW, u32 cig_stride, u32 max_len, double vali
 int pe_seed_resident_waves(size_t lds, bool coop);
 int pe_mate_resident_waves(size_t lds, bool big);
 hipError_t launch_pe_seed(const PeArgs &a, size_t lds, u32 grid, bool timed, hipStream_t st);
-hipError_t launch_pe_mate(const PeArgs &a, size_t lds, u32 grid, bool big, bool timed, hipStream_t st);
+hipError_t launch_pe_mate(const PeArgs &a, size_t lds, u32 grid, bool big, bool timed, hipStream_t st, bool text = false);
 #ifndef ABM_PE_TIER1_CAP
 #define ABM_PE_TIER1_CAP 128
 #endif

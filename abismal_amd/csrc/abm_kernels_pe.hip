@@ -16,6 +16,7 @@
 #include <climits>
 #include "abm_kernels_core.hpp"
 #include "abm_pe_set.hpp"
+#include "abm_sam.hpp"
 
 // Waves per SIMD the pair kernels are compiled for: 4 (128 registers per lane), and for the production kernels on the
 // bit planes also 3 (170 registers): with 2x150-base pairs the LDS of a wave allows 13 waves per CU anyway, and the
@@ -70,7 +71,7 @@ enum : int { kWhole = 0, kSeed = 1, kMate = 2 };
 #define ABM_PE_RADIX_SORT_MIN 512
 #endif
 constexpr int kRadixSortMin = ABM_PE_RADIX_SORT_MIN;  // tier 2: lists longer than this are sorted by radix passes, shorter ones by the bitonic network
-template <bool BIG, bool COOP, bool LONG = false, int PHASE = kWhole, bool REC = false> struct PeWave {
+template <bool BIG, bool COOP, bool LONG = false, int PHASE = kWhole, bool REC = false, bool TEXT = false> struct PeWave {
   const PeArgs &a;
   WaveLds lds;      // qpk/qbits point at end 0; end 1 follows at +4W / +4WB
   PeLds pl;
@@ -93,6 +94,7 @@ template <bool BIG, bool COOP, bool LONG = false, int PHASE = kWhole, bool REC =
   int max_set;
   u32 *stage_pos;  // seed kernel: this wave's staging area for a list that outgrows its LDS slot
   i16 *stage_d;
+  u32 *fin;        // TEXT: each end's final CIGAR's first kSeCap ops in LDS ([2][kSeCap]; CigarSink::fin)
 
   // (ends are run-time values -- the orientation calls are ONE piece of code looped over -- so the two-element register
   // arrays are read and written through selects, never indexed)
@@ -105,7 +107,10 @@ template <bool BIG, bool COOP, bool LONG = false, int PHASE = kWhole, bool REC =
     return w;
   }
   __device__ __forceinline__ u32 *cig_of(int end, u64 r) const { return (end ? a.cig2 : a.cig1) + r * a.cig_stride; }
-  __device__ __forceinline__ CigarSink sink() const { return CigarSink{a.cig_stride, a.ctmp_cap, a.cig_arena, a.cig_arena_count, a.cig_arena_cap}; }
+  __device__ __forceinline__ CigarSink sink(int end) const {
+    if constexpr (TEXT) return CigarSink{a.cig_stride, a.ctmp_cap, a.cig_arena, a.cig_arena_count, a.cig_arena_cap, fin + end * kSeCap};
+    else return CigarSink{a.cig_stride, a.ctmp_cap, a.cig_arena, a.cig_arena_count, a.cig_arena_cap};
+  }
 
   // ---- one end of one orientation call: both seed passes, then freeze the set ----
   template <bool TIMED> __device__ __forceinline__ void seed_end(int which, int end, bool rc, bool ar) {
@@ -467,6 +472,7 @@ template <bool BIG, bool COOP, bool LONG = false, int PHASE = kWhole, bool REC =
     int n_ins = 0, n_del = 0;
     if (d == 0) {  // align<true> returns at once; build_cigar gives the default CIGAR (:404-409)
       if (lane == 0) cig_out[0] = static_cast<u32>(Ln) << 4;
+      if constexpr (TEXT) { if (lane == 0) fin[end * kSeCap] = static_cast<u32>(Ln) << 4; }
       nops = 1;
       alen = static_cast<u32>(Ln);
     }
@@ -494,7 +500,7 @@ template <bool BIG, bool COOP, bool LONG = false, int PHASE = kWhole, bool REC =
       const int bc = static_cast<int>(0xFFu - static_cast<u32>(topk & 0xFFu));
       const int sc = static_cast<i16>(static_cast<int>(topk >> 32));
       wave_sync();
-      wave_cigar(lds.tb, lds.ctmp, Ln, d, md, sc, br, bc, cig_out, sink(), nops, n_ins, n_del, alen, pos,
+      wave_cigar(lds.tb, lds.ctmp, Ln, d, md, sc, br, bc, cig_out, sink(end), nops, n_ins, n_del, alen, pos,
                  overflow);
       wave_sync();
     }
@@ -733,16 +739,109 @@ template <bool BIG, bool COOP, bool LONG = false, int PHASE = kWhole, bool REC =
   }
 };
 
+// ---- a pair's SAM records written by the wave that finished it (PeArgs::sam_tail) -----------------------------------
+// select_output (src/abismal.cpp:1073-1088; the CLI's emit_pe / emit_se): the proper pair's two records (format_pe,
+// :648-773), or else up to two single-end records (format_se, :481-545), each minus QNAME.  The line of end e of pair r
+// goes to sam_tail + (2 r + e) * sam_stride, its length to sam_len[2 r + e] (0: no record), the pair's kind to
+// sam_kind[r]: kPeTextPair, kPeTextSingles (also a proper pair whose ends cannot both be located on one chromosome), or
+// kPeTextHost -- an end beyond kLdsReadLen bases, a CIGAR beyond `fin`, a line beyond its slot: the host formats the
+// whole pair.  line: the traceback table's place, idle once both CIGARs are out (at least sam_stride bytes: the host
+// checks, sam_line_room); fin: each end's last traceback's first kSeCap ops.
+__device__ __forceinline__ void format_pe_tails(const PeArgs &a, u8 *line, const u32 *fin, u64 r, const u32 L[2],
+                                                const PairBest &best, const Hit &h1, const Hit &h2, const u32 n_ops[2]) {
+  const int lane = lane_id();
+  const bool allow = a.sam_allow_ambig != 0;
+  u8 kind = kPeTextSingles;
+  u32 len[2] = {0u, 0u};
+  wave_sync();  // (fin was written by whichever lanes stored the CIGARs)
+  if (a.lens1[r] > kLdsReadLen || a.lens2[r] > kLdsReadLen) kind = kPeTextHost;  // (the long-end launch's pair, or too long)
+  else if (best.p1 != 0 && (allow || !(best.f1 & kFlagAmbig))) {  // format_pe
+    if (n_ops[0] == 0 || n_ops[1] == 0 || n_ops[0] > kSeCap || n_ops[1] > kSeCap) kind = kPeTextHost;
+    else {
+      const u32 rl1 = sam_ref_len(fin, n_ops[0]), rl2 = sam_ref_len(fin + kSeCap, n_ops[1]);
+      u32 ch1 = 0, ch2 = 0, b1 = 0, b2 = 0;
+      if (sam_locate(a.ix, best.p1, rl1, ch1, b1) && sam_locate(a.ix, best.p2, rl2, ch2, b2) && ch1 == ch2) {
+        kind = kPeTextPair;
+        b1 = best.p1 - b1; b2 = best.p2 - b2;
+        const u32 e2 = b2 + rl2;
+        const bool rc1 = (best.f1 & kFlagRC) != 0, rc2 = (best.f2 & kFlagRC) != 0;
+        const int isize = rc1 ? static_cast<int>(b1) - static_cast<int>(e2) : static_cast<int>(e2) - static_cast<int>(b1);
+        const u32 amb = (allow && (best.f1 & kFlagAmbig)) ? 0x100u : 0u;
+        const u32 f1 = 0x1u | 0x2u | 0x40u | (rc1 ? 0x10u : 0u) | (rc2 ? 0x20u : 0u) | amb;
+        const u32 f2 = 0x1u | 0x2u | 0x80u | (rc2 ? 0x10u : 0u) | (rc1 ? 0x20u : 0u) | amb;
+        for (int e = 0; e < 2; ++e) {
+          SamWriter o{line, 0, a.sam_stride};
+          o.put('\t');
+          o.put_uint(e ? f2 : f1);
+          o.put('\t');
+          o.put_chrom(a.ix, ch1);
+          o.put('\t');
+          o.put_uint((e ? b2 : b1) + 1u);
+          o.put_str("\t255\t", 5);
+          o.put_cigar(fin + e * kSeCap, e ? n_ops[1] : n_ops[0]);
+          o.put_str("\t=\t", 3);
+          o.put_uint((e ? b1 : b2) + 1u);
+          o.put('\t');
+          o.put_int(e ? -isize : isize);
+          o.put('\t');
+          o.put_seq((e ? a.blob2 + a.off2[r] : a.blob1 + a.off1[r]), e ? L[1] : L[0], e ? rc2 : rc1);
+          o.put_tags(static_cast<i16>(e ? best.d2 : best.d1), ((e ? best.f2 : best.f1) & kFlagARich) != 0);
+          if (o.w > o.cap) { kind = kPeTextHost; break; }
+          o.flush(reinterpret_cast<u32 *>(a.sam_tail + (2 * r + e) * a.sam_stride));
+          wave_sync();  // (the next line is built where this one was read from)
+          len[e] = o.w;
+        }
+      }
+    }
+  }
+  if (kind == kPeTextSingles) {  // format_se of either end (the hits the fallback left; none if it did not run)
+    for (int e = 0; e < 2; ++e) {
+      const Hit &h = e ? h2 : h1;
+      const u32 nops = e ? n_ops[1] : n_ops[0];
+      const bool ambig = (h.flags & kFlagAmbig) != 0;
+      if (h.pos == 0 || (ambig && !allow)) continue;
+      if (nops == 0 || nops > kSeCap) { kind = kPeTextHost; break; }
+      u32 chrom = 0, c0 = 0;
+      if (!sam_locate(a.ix, h.pos, sam_ref_len(fin + e * kSeCap, nops), chrom, c0)) continue;
+      const bool rc = (h.flags & kFlagRC) != 0;
+      SamWriter o{line, 0, a.sam_stride};
+      o.put('\t');
+      o.put_uint((rc ? 0x10u : 0u) | ((allow && ambig) ? 0x100u : 0u));
+      o.put('\t');
+      o.put_chrom(a.ix, chrom);
+      o.put('\t');
+      o.put_uint(h.pos - c0 + 1u);
+      o.put_str("\t255\t", 5);
+      o.put_cigar(fin + e * kSeCap, nops);
+      o.put_str("\t*\t0\t0\t", 7);
+      o.put_seq((e ? a.blob2 + a.off2[r] : a.blob1 + a.off1[r]), e ? L[1] : L[0], rc);
+      o.put_tags(h.diffs, (h.flags & kFlagARich) != 0);
+      if (o.w > o.cap) { kind = kPeTextHost; break; }
+      o.flush(reinterpret_cast<u32 *>(a.sam_tail + (2 * r + e) * a.sam_stride));
+      wave_sync();
+      len[e] = o.w;
+    }
+  }
+  if (kind == kPeTextHost) len[0] = len[1] = 0;
+  if (lane == 0) {
+    store_out(a.sam_len + 2 * r, len[0]);
+    store_out(a.sam_len + 2 * r + 1, len[1]);
+    a.sam_kind[r] = kind;
+  }
+}
+
 // REC: the seed passes filter on the window records (DevIndex::wrec) -- a launch none of whose ends is longer than they serve
-template <bool BIG, bool TIMED, bool COOP, int WPS, bool LONG = false, int PHASE = kWhole, bool REC = false>
+// TEXT: the pair's SAM records are written as well (PeArgs::sam_tail, format_pe_tails)
+template <bool BIG, bool TIMED, bool COOP, int WPS, bool LONG = false, int PHASE = kWhole, bool REC = false, bool TEXT = false>
 __global__ __launch_bounds__(64, WPS) void map_pe_kernel(PeArgs a) {
   static_assert(!REC || (COOP && PHASE != kMate), "window records feed the cooperative filter of the seed passes");
   static_assert(!LONG || (BIG && !COOP && !TIMED && PHASE == kWhole), "the long-end launch: tier 2's lists, nibble filter, no stamps");
   static_assert(PHASE != kSeed || !BIG, "the seed kernel keeps its lists in LDS (and its staging area)");
   static_assert(PHASE != kMate || !COOP, "the mate kernels fetch no candidate windows");
+  static_assert(!TEXT || (!LONG && !TIMED && PHASE != kSeed), "SAM text: the launches that finish pairs in LDS");
   extern __shared__ __align__(16) unsigned char smem[];
   const int lane = lane_id();
-  PeWave<BIG, COOP, LONG, PHASE, REC> w{a};
+  PeWave<BIG, COOP, LONG, PHASE, REC, TEXT> w{a};
   WaveLds &lds = w.lds;
   lds.W = a.W; lds.WB = a.WB; lds.GW = a.GW;
   u32 *after_heap;
@@ -826,6 +925,7 @@ __global__ __launch_bounds__(64, WPS) void map_pe_kernel(PeArgs a) {
   lds.G = a.G;
   if constexpr (PHASE != kMate) { lds.smark[lane] = 0; lds.smark[64 + lane] = 0; }
   else lds.mark = reinterpret_cast<u16 *>(after_heap);  // (no seed passes: no segment marks)
+  if constexpr (TEXT) w.fin = reinterpret_cast<u32 *>(lds.mark + 64);  // (after the 64 marks: kPeFinBytes more LDS)
   w.seg_epoch = 0;
 
   w.P.heap = w.pl.heap;
@@ -968,13 +1068,14 @@ __global__ __launch_bounds__(64, WPS) void map_pe_kernel(PeArgs a) {
         u32 nops = 0;
         Hit &h = e ? h2 : h1;
         u32 n_single = 0;
-        choose_se<LONG>(a.ix, we, w.L[e], a.valid_frac / 2, w.se[e], h, w.cig_of(e, r), w.sink(), nops,
+        choose_se<LONG>(a.ix, we, w.L[e], a.valid_frac / 2, w.se[e], h, w.cig_of(e, r), w.sink(e), nops,
                         w.overflow, w.n_aln, n_single);
         if (nops != 0) w.n_ops[e] = nops;  // whatever traceback ran last owns the slot (A.10)
       }
       ABM_STAMP(tf1);
       if (TIMED) t_fb += tf1 - tf0;
     }
+    if constexpr (TEXT) format_pe_tails(a, lds.tb, w.fin, r, w.L, best, h1, h2, w.n_ops);
     if (lane == 0) {
       u32 *po = reinterpret_cast<u32 *>(a.pairs) + r * 5;
       po[0] = static_cast<u32>(static_cast<u16>(static_cast<i16>(best.aln_score)));
@@ -1092,6 +1193,8 @@ int pe_waves_per_simd(size_t lds, bool timed, bool coop) {
   return (!timed && coop && lds != 0 && (160u * 1024u) / lds <= 13u) ? 3 : ABM_PE_WAVES_PER_SIMD;
 }
 
+int pe_text_waves_per_simd() { return ABM_PE_WAVES_PER_SIMD; }
+
 int pe_resident_waves(size_t lds, bool big, int wps) {
   int per_cu = 0, dev = 0;
   hipDeviceProp_t prop;
@@ -1126,8 +1229,16 @@ static void launch_pe_variant(const PeArgs &a, size_t lds, u32 grid, int wps, hi
   else hipLaunchKernelGGL((map_pe_kernel<BIG, TIMED, false, ABM_PE_WAVES_PER_SIMD>), dim3(grid), dim3(64), lds, st, a);
 }
 
-hipError_t launch_map_pe(const PeArgs &a, size_t lds, u32 grid, bool big, bool timed, int wps, hipStream_t st) {
+hipError_t launch_map_pe(const PeArgs &a, size_t lds, u32 grid, bool big, bool timed, int wps, hipStream_t st, bool text) {
   if (grid == 0) return hipSuccess;
+  if (text) {
+    // SAM text: the builds on the bit planes (a.G != 0), four waves per SIMD, the planes for ends the window records would
+    // serve as well (the same candidates); lds includes kPeFinBytes
+    if (timed || a.G == 0) return hipErrorInvalidValue;
+    if (big) hipLaunchKernelGGL((map_pe_kernel<true, false, true, ABM_PE_WAVES_PER_SIMD, false, kWhole, false, true>), dim3(grid), dim3(64), lds, st, a);
+    else hipLaunchKernelGGL((map_pe_kernel<false, false, true, ABM_PE_WAVES_PER_SIMD, false, kWhole, false, true>), dim3(grid), dim3(64), lds, st, a);
+    return hipGetLastError();
+  }
   if (big && timed) launch_pe_variant<true, true>(a, lds, grid, wps, st);
   else if (big) launch_pe_variant<true, false>(a, lds, grid, wps, st);
   else if (timed) launch_pe_variant<false, true>(a, lds, grid, wps, st);
@@ -1235,8 +1346,14 @@ hipError_t launch_pe_seed(const PeArgs &a, size_t lds, u32 grid, bool timed, hip
   }
   return hipGetLastError();
 }
-hipError_t launch_pe_mate(const PeArgs &a, size_t lds, u32 grid, bool big, bool timed, hipStream_t st) {
+hipError_t launch_pe_mate(const PeArgs &a, size_t lds, u32 grid, bool big, bool timed, hipStream_t st, bool text) {
   if (grid == 0) return hipSuccess;
+  if (text) {  // (SAM text: lds includes kPeFinBytes)
+    if (timed) return hipErrorInvalidValue;
+    if (big) hipLaunchKernelGGL((map_pe_kernel<true, false, false, kPeMateWps, false, kMate, false, true>), dim3(grid), dim3(64), lds, st, a);
+    else hipLaunchKernelGGL((map_pe_kernel<false, false, false, kPeMateWps, false, kMate, false, true>), dim3(grid), dim3(64), lds, st, a);
+    return hipGetLastError();
+  }
   if (big) {
     if (timed) hipLaunchKernelGGL((map_pe_kernel<true, true, false, kPeMateWps, false, kMate>), dim3(grid), dim3(64), lds, st, a);
     else hipLaunchKernelGGL((map_pe_kernel<true, false, false, kPeMateWps, false, kMate>), dim3(grid), dim3(64), lds, st, a);

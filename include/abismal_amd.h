@@ -193,6 +193,22 @@ int abm_ctx_slice_results(abm_ctx *ctx, uint64_t lo, uint64_t hi, abm_hit *out_r
  * when the launch wrote none.  Valid until the callback returns. */
 int abm_ctx_set_sam_tails(abm_ctx *ctx, int enable, int allow_ambig);
 int abm_ctx_slice_sam_tails(abm_ctx *ctx, uint64_t lo, uint64_t hi, const char **tails, uint32_t *stride, const uint32_t **lens);
+/* The same for pairs: with tails enabled, abm_map_pe_batch's kernels also write, for every pair, the records that
+ * select_output prints (src/abismal.cpp:1073-1088), minus QNAME -- a proper pair's two records (format_pe, :648-773:
+ * flags 0x1|0x2|0x40 / 0x80, 0x10 / 0x20 by strand, 0x100 with allow_ambig; RNEXT "=", PNEXT the mate's POS, TLEN
+ * +-isize; each end its own NM and CV), or else up to two single-end records (format_se: RNEXT "*", 0, 0).  After the
+ * call, abm_ctx_pe_sam_tails hands out the context's pinned buffers for pairs [lo, hi) of that batch: the tail of end e
+ * of pair lo + k at *tails + (2k + e) * *stride, lens[2k + e] bytes long (0: that end has no record), and kinds[k]:
+ *   0     the pair's two records;
+ *   1     single-end fallback records (also a pair whose ends cannot both be located on one chromosome: unmapped as a
+ *         pair);
+ *   0xFF  nothing written: format this pair from the batch's results as before (an end of more than 1024 bases, a CIGAR
+ *         of more than 50 ops, a line beyond its slot).
+ * The stride is computed per batch from its longest end.  *tails (and lens, kinds) is NULL when the batch wrote none:
+ * text needs a genome without IUPAC letters (the filter on bit planes), no phase stamps, and a slot that fits the LDS a
+ * line is built in (the single-end launches apply the same guard).  Valid until the context's next mapping call. */
+int abm_ctx_pe_sam_tails(abm_ctx *ctx, uint64_t lo, uint64_t hi, const char **tails, uint32_t *stride,
+                         const uint32_t **lens, const uint8_t **kinds);
 
 /* Same computation with every buffer already resident in HBM (d_* are device
  * pointers), enqueued on `stream` (a hipStream_t; NULL = default stream) and
@@ -249,7 +265,8 @@ int abm_ctx_pe_split_stats(abm_ctx *ctx, uint64_t out[4]);
 /* HIP-event brackets (abm_ctx_set_timing) the context's last paired-end call recorded, in launch order: split -- seed,
  * mate (LDS lists), mate (lists in device memory), whole pairs = 4; unsplit -- tier 1, tier 2 = 2. */
 uint32_t abm_ctx_pe_timed_launches(const abm_ctx *ctx);
-/* page-locked host memory the context holds for results on their way out (its pinned staging buffers), bytes */
+/* page-locked host memory the context holds for results on their way out (its pinned staging buffers, SAM text
+ * included), bytes */
 uint64_t abm_ctx_pinned_bytes(const abm_ctx *ctx);
 
 /* the arena of CIGARs longer than their slot left by the context's last device call (waits for it) */
