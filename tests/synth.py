@@ -43,13 +43,17 @@ def repeat_rich_genome(path, seed=3, n_chroms=3, chrom_len=1_500_000, iupac=0):
             f.write(b"\n".join(bytes(seq[i:i + 70]) for i in range(0, chrom_len, 70)) + b"\n")
 
 
+def read_chroms(fasta):
+    """the chromosomes of a FASTA as upper-case uint8 arrays"""
+    return [np.frombuffer(rec.split(b"\n", 1)[1].replace(b"\n", b"").upper(), dtype=np.uint8)
+            for rec in open(fasta, "rb").read().split(b">")[1:]]
+
+
 def mutated_reads(fasta, n, L, seed, mut=0.02, bis=0.95, pbat_frac=0.0, n_frac=0.02):
     """Reads drawn from a FASTA with substitutions/indels and bisulfite conversion;
     a fraction carry N bases (leading/trailing/internal) and a few are too short."""
     rng = np.random.default_rng(seed)
-    chroms = []
-    for rec in open(fasta, "rb").read().split(b">")[1:]:
-        chroms.append(np.frombuffer(rec.split(b"\n", 1)[1].replace(b"\n", b"").upper(), dtype=np.uint8))
+    chroms = read_chroms(fasta)
     reads = []
     for _ in range(n):
         ch = chroms[int(rng.integers(0, len(chroms)))]
@@ -103,13 +107,60 @@ def trim_like_readloader(reads):
     return out
 
 
+def cut_pairs_ragged(r1, r2, rng, lo, hi):
+    """Pairs generated at the batch's longest length, both ends of a pair truncated independently to lo..hi bases (uniform,
+    both included); the last pair is kept whole so that the batch's longest end stays.  Apply trim_like_readloader afterwards."""
+    out1 = [a[: int(rng.integers(lo, hi + 1))] for a in r1[:-1]] + [r1[-1]]
+    out2 = [b[: int(rng.integers(lo, hi + 1))] for b in r2[:-1]] + [r2[-1]]
+    return out1, out2
+
+
+def cut_pairs_fixed(r1, r2, L1, L2):
+    """Unequal ends: every end 1 truncated to L1 bases and every end 2 to L2.  Apply trim_like_readloader afterwards."""
+    return [a[:L1] for a in r1], [b[:L2] for b in r2]
+
+
+def pairs_at_n_runs(chroms, lengths, seed=4, mirrored=False, straddle=False, unmated=False):
+    """Exact, fully converted pairs on a repeat_rich_genome: one end cut at distance 0..24 from the long N run in the middle
+    of each chromosome, left of it and right of it, the other end 150-400 bases further out on the opposite strand.
+    mirrored: also the same fragments read from the other strand, so that either end is the one at the run on both sides.
+    straddle: also pairs whose ends lie either side of the short (LCG-filled) N run at 1000-1100, both strands.
+    unmated: also pairs with one end at the long run and the other 50,000 bases further out, too far to be its mate: each
+    end can only be reported on its own (fallback hits)."""
+    r1, r2 = [], []
+    rng = np.random.default_rng(seed)
+
+    def add(fwd, rev):
+        r1.append(bytes(fwd).decode().replace("C", "T"))
+        r2.append(bytes(COMP[rev[::-1]]).decode().replace("G", "A"))
+        if mirrored:
+            r1.append(bytes(COMP[rev[::-1]]).decode().replace("C", "T"))
+            r2.append(bytes(fwd).decode().replace("G", "A"))
+
+    for ch in chroms:
+        mid = len(ch) // 2
+        for L in lengths:
+            for k in range(25):
+                gap = int(rng.integers(150, 400))
+                a, b = ch[mid - L - k: mid - k], ch[mid - k - gap - L: mid - k - gap]         # left of the run
+                c, d = ch[mid + 3000 + k: mid + 3000 + k + L], ch[mid + 3000 + k + gap: mid + 3000 + k + gap + L]  # right of it
+                for fwd, rev in ((b, a), (c, d)):
+                    add(fwd, rev)
+            if unmated:
+                for k in range(0, 25, 4):
+                    add(ch[mid - k - 50_000 - L: mid - k - 50_000], ch[mid - L - k: mid - k])
+                    add(ch[mid + 3000 + k: mid + 3000 + k + L], ch[mid + 3000 + k + 50_000: mid + 3000 + k + 50_000 + L])
+            if straddle:
+                for k in range(0, 25, 3):
+                    add(ch[1000 - L - k: 1000 - k], ch[1100 + k: 1100 + k + L])
+    return r1, r2
+
+
 def mutated_pairs(fasta, n, L, seed, mut=0.02, bis=0.95, frag=(120, 600)):
     """Read pairs from random fragments: read 1 = fragment start, read 2 = revcomp of its end;
     conversion C->T on the fragment strand (so read 2 looks G->A), with mutations and some Ns."""
     rng = np.random.default_rng(seed)
-    chroms = []
-    for rec in open(fasta, "rb").read().split(b">")[1:]:
-        chroms.append(np.frombuffer(rec.split(b"\n", 1)[1].replace(b"\n", b"").upper(), dtype=np.uint8))
+    chroms = read_chroms(fasta)
     out1, out2 = [], []
     for _ in range(n):
         ch = chroms[int(rng.integers(0, len(chroms)))]

@@ -413,8 +413,7 @@ def test_windows_that_reach_into_an_n_run(oracle, workdir):
     synth.repeat_rich_genome(fa, seed=11, n_chroms=2, chrom_len=400_000)
     idx = os.path.join(workdir, "nrun.idx")
     oracle.index_build(fa, idx, threads=4)
-    chroms = [np.frombuffer(rec.split(b"\n", 1)[1].replace(b"\n", b"").upper(), dtype=np.uint8)
-              for rec in open(fa, "rb").read().split(b">")[1:]]
+    chroms = synth.read_chroms(fa)
     reads = []
     for ch in chroms:
         mid = len(ch) // 2
@@ -438,18 +437,8 @@ def test_windows_that_reach_into_an_n_run(oracle, workdir):
     assert (res["pos"] != 0).mean() > 0.5
     # the same for pairs: end 1 cut at the edge of the N run, end 2 from 150-400 bases further out, opposite strand
     from tests.test_gpu_pe_parity import compare_pe
-    r1, r2 = [], []
-    rng = np.random.default_rng(4)
-    for ch in chroms:
-        mid = len(ch) // 2
-        for L in (100, 150):
-            for k in range(25):
-                gap = int(rng.integers(150, 400))
-                a, b = ch[mid - L - k: mid - k], ch[mid - k - gap - L: mid - k - gap]         # left of the run
-                c, d = ch[mid + 3000 + k: mid + 3000 + k + L], ch[mid + 3000 + k + gap: mid + 3000 + k + gap + L]  # right of it
-                for fwd, rev in ((b, a), (c, d)):
-                    r1.append(bytes(fwd).decode().replace("C", "T"))
-                    r2.append(bytes(synth.COMP[rev[::-1]]).decode().replace("G", "A"))
+    # (per filter, end length and record size, and with either end at the run: tests/test_gpu_pe_filter_paths.py)
+    r1, r2 = synth.pairs_at_n_runs(chroms, (100, 150), seed=4)
     gpu = ctx.map_pe(r1, r2)
     oix = oracle.index_load(idx)
     try:
