@@ -200,6 +200,10 @@ class Context:
             self._lib.abm_ctx_destroy(self.handle)
             self.handle = None
 
+    def reserve(self, n, max_len, paired=False):
+        """abm_ctx_reserve: every workspace for batches of up to n reads (pairs) of up to max_len bases, up front"""
+        _check(self._lib.abm_ctx_reserve(self.handle, int(n), int(max_len), 1 if paired else 0))
+
     def seed_extension(self):
         """(letters of the 2-letter table, letters of the 3-letter tables, bytes) resident on this context's device"""
         a, b, n = C.c_uint32(), C.c_uint32(), C.c_uint64()

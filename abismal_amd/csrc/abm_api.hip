@@ -71,9 +71,13 @@ void note_regrowth(const char *what, size_t from, size_t to) {
     std::fprintf(stderr, "[abm host] %s buffer regrown %zu -> %zu bytes (frees wait for the device)\n", what, from, to);
 }
 
-template <class T> struct DevBuf {  // grow-only device allocation
+template <class T> struct DevBuf {  // grow-only device allocation, freed with its owner
   T *p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { release(); }
   void reserve(size_t n) {
     if (n <= cap) return;
     if (p) { note_regrowth("device", cap * sizeof(T), n * sizeof(T)); HIPCHK(hipFree(p)); }
@@ -88,6 +92,10 @@ template <class T> struct DevBuf {  // grow-only device allocation
 template <class T> struct HostBuf {
   T *p = nullptr;
   size_t cap = 0;
+  HostBuf() = default;
+  HostBuf(const HostBuf &) = delete;
+  HostBuf &operator=(const HostBuf &) = delete;
+  ~HostBuf() { release(); }
   void reserve(size_t n) {
     if (n <= cap) return;
     if (p) { note_regrowth("pinned host", cap * sizeof(T), n * sizeof(T)); HIPCHK(hipHostFree(p)); }
@@ -139,7 +147,6 @@ struct abm_ctx {
   hipStream_t stream = nullptr;  // the host-buffer entry points run on the context's own stream
   std::mutex *kernel_turn = nullptr;
   abm::u32 *drained = nullptr;   // pinned, device-mapped: the mapping kernel has handed out its last read
-  bool signal_drained = false;  // set by the host-buffer entry point around its launch
   // per-batch workspaces (grow-only; sized by the largest batch seen)
   DevBuf<abm::u64> packed, packed2;
   DevBuf<abm::u32> lens2, subset, subset_count, payload1, payload2, list2, heap2, log2;
@@ -154,12 +161,7 @@ struct abm_ctx {
   int pe_split = -1;     // -1: default (split), 0: tier 1 unsplit, 1: split
   uint32_t pe_scap = 0;  // 0: default
   uint32_t pe_timed_launches = 0;  // HIP-event brackets the last paired-end call recorded (abm_ctx_set_timing)
-  DevBuf<abm::Hit> pe_out;  // staging: pairs (20 B each) then se1, se2
-  DevBuf<abm::u32> cig2h, cig_n2h;
   DevBuf<char> blob2;
-  DevBuf<unsigned long long> coff;
-  DevBuf<char> scan_tmp;
-  DevBuf<abm::u32> cblob;
   DevBuf<abm::u64> off2;
   DevBuf<abm::u32> lens, order, class33;
   DevBuf<abm::u32> long_list, long_count, long_ctmp;  // the long-read launch (se_long_reads): listed reads, per-wave scratch
@@ -180,10 +182,8 @@ struct abm_ctx {
   DevBuf<abm::u32> slice_first_d, slice_left, slice_hist;
   DevBuf<abm::u16> slice_id;
   HostBuf<abm::u32> h_slice_first, h_slice_done;
-  uint32_t sliced_n = 0;           // slices of the launch being set up (0 = an ordinary launch)
   uint32_t sliced_stride = 0;      // slot width of the results abm_ctx_slice_results reads
   uint64_t sliced_reads = 0;
-  bool host_results = false;        // set by abm_map_se_batch around its launches: arena and summary words in pinned memory
   // SAM text written by the single-end kernel (abm_ctx_set_sam_tails): the line after QNAME per read, in pinned memory
   bool sam_on = false;
   int sam_allow_ambig = 0;
@@ -204,8 +204,7 @@ struct abm_ctx {
   // staging for the host-buffer entry points
   DevBuf<char> blob;
   DevBuf<abm::u64> off;
-  DevBuf<abm::Hit> res;
-  DevBuf<abm::u32> cig, cig_n, status;
+  DevBuf<abm::u32> status;
   // optional HIP-event timing of the mapping kernel (abm_ctx_set_timing)
   bool timing = false;
   abm::u32 *read_cycles = nullptr;  // caller-owned device array for the diagnostic kernel
@@ -336,28 +335,123 @@ void check_params(const abm_params *p) {
   if (!(p->valid_frac >= 0.0 && p->valid_frac <= 1.0)) throw std::invalid_argument("valid_frac out of range");
 }
 
-// HIP-event bracket around one mapping-kernel launch (abm_ctx_set_timing); returns the closing event
-hipEvent_t begin_timed(abm_ctx *ctx, hipStream_t st) {
-  if (!ctx->timing) return nullptr;
-  if (ctx->events_used == ctx->events.size()) {
-    hipEvent_t x, y;
-    HIPCHK(hipEventCreate(&x));
-    HIPCHK(hipEventCreate(&y));
-    ctx->events.emplace_back(x, y);
+// What a host-buffer entry point asks of its launch (the device entry points pass a default one)
+struct HostMode {
+  bool host_results = false;    // arena, summary words and SAM text in pinned memory
+  bool signal_drained = false;  // the mapping kernel tells the host when it has handed out its last read
+  uint32_t n_slices = 0;        // results leave slice by slice (0 = an ordinary launch)
+};
+
+// What every launch derives from its reads' length and the filter's fraction.  Reads beyond kLdsReadLen bases are left
+// out of the ordinary launches, whose workspaces, LDS and filter stay what the batch's ordinary reads need; the long
+// launches (kLong) take max_len as it is and keep traceback tables and window loads out of LDS.
+enum class ShapeKind { kSingle, kPair, kLong };
+struct LaunchShape {
+  abm::u32 eff_len, W, WB, GW, tb_extra, G, ctmp_cap;
+  double size_frac;
+};
+LaunchShape launch_shape(const abm_ctx *ctx, abm::u32 max_len, double valid_frac, ShapeKind kind) {
+  LaunchShape s{};
+  const bool lng = kind == ShapeKind::kLong;
+  s.eff_len = lng ? max_len : std::min<abm::u32>(std::max<abm::u32>(max_len, 1), abm::kLdsReadLen);
+  s.W = words_for(s.eff_len);
+  s.WB = bitwords_for(s.eff_len);
+  // IUPAC genome letters can drive a Hamming sum below zero, which the reference turns into the
+  // widest band (61); size the LDS for it only when such letters exist
+  s.size_frac = ctx->ix->h.multibit_genome ? 1.0 : valid_frac;
+  s.GW = abm::se_window_words(s.eff_len, s.size_frac);
+  s.tb_extra = lng ? 0u : abm::tb_extra_bytes(s.GW, s.eff_len, s.size_frac);
+  s.ctmp_cap = s.eff_len + 2;
+  // cooperative window loads from the genome's bit planes (hamming_planes): not for genomes with IUPAC letters (no
+  // planes; their admission rule needs full_compare's word-by-word running sums) nor for reads beyond 448 bases;
+  // G lanes x 64 bases cover a window of eff_len + 63 bases, and pairs start at four lanes.
+  // ABM_COOP_WINDOWS=0 switches them off, =4 widens the single-end launch's two lanes to four (experiments)
+  if (!lng && ctx->dix.planes[0] != nullptr) {
+    const abm::u32 L = s.eff_len;
+    s.G = kind == ShapeKind::kSingle && L <= 2 * abm::kPlaneBlock ? 2u : (L <= 4 * abm::kPlaneBlock - 64 ? 4u : (L <= 8 * abm::kPlaneBlock - 64 ? 8u : 0u));
+    if (const char *e = experiment_env("ABM_COOP_WINDOWS")) {
+      if (e[0] == '0') s.G = 0;
+      else if (e[0] == '4' && s.G == 2) s.G = 4;
+    }
   }
-  const hipEvent_t e0 = ctx->events[ctx->events_used].first, e1 = ctx->events[ctx->events_used].second;
-  ++ctx->events_used;
-  HIPCHK(hipEventRecord(e0, st));
-  return e1;
+  return s;
+}
+
+// a work counter of its own for every launch: a small ring, so launches queued on different streams never share one
+unsigned long long *fresh_counter(abm_ctx *ctx, hipStream_t st) {
+  unsigned long long *counter = ctx->next_read.p + (ctx->launch_seq++ & 63u);
+  HIPCHK(hipMemsetAsync(counter, 0, sizeof(unsigned long long), st));
+  return counter;
+}
+
+// launch() between a pair of HIP events when the mapping kernels are timed (abm_ctx_set_timing)
+template <class F> void timed_launch(abm_ctx *ctx, hipStream_t st, F &&launch) {
+  hipEvent_t e1 = nullptr;
+  if (ctx->timing) {
+    if (ctx->events_used == ctx->events.size()) {
+      hipEvent_t x, y;
+      HIPCHK(hipEventCreate(&x));
+      HIPCHK(hipEventCreate(&y));
+      ctx->events.emplace_back(x, y);
+    }
+    const hipEvent_t e0 = ctx->events[ctx->events_used].first;
+    e1 = ctx->events[ctx->events_used].second;
+    ++ctx->events_used;
+    HIPCHK(hipEventRecord(e0, st));
+  }
+  launch();
+  if (e1) HIPCHK(hipEventRecord(e1, st));
+}
+
+// The arena for the CIGARs that outgrow their slot, `ops` of them unless the context asks for more (an arena that
+// overflows costs a second mapping of the batch); pinned = in host memory, like the rest of a host-buffer entry
+// point's results, with the two summary words and the counter of finished waves that publish them
+void arena_reserve(abm_ctx *ctx, size_t ops, bool pinned) {
+  const size_t want = std::min<size_t>(std::max<size_t>(ctx->arena_want, std::max<size_t>(1u << 16, ops)), 0xFFFFFF00u);
+  ctx->cig_arena_count.reserve(1);
+  if (pinned) { ctx->h_arena.reserve(want); ctx->h_tail.reserve(2); ctx->finished.reserve(1); }
+  else ctx->cig_arena.reserve(want);
+}
+template <class Args> void arena_setup(abm_ctx *ctx, Args &a, bool pinned, hipStream_t st) {
+  HIPCHK(hipMemsetAsync(ctx->cig_arena_count.p, 0, 4, st));
+  a.cig_arena_count = ctx->cig_arena_count.p;
+  if (pinned) ctx->h_tail.p[0] = ctx->h_tail.p[1] = 0;
+  a.cig_arena = pinned ? ctx->h_arena.p : ctx->cig_arena.p;
+  a.cig_arena_cap = static_cast<abm::u32>(std::min<size_t>(pinned ? ctx->h_arena.cap : ctx->cig_arena.cap, 0xFFFFFF00u));
+}
+
+// Bytes of a read's SAM-text slot if the single-end launch writes the text itself (abm_ctx_set_sam_tails), else 0: only
+// the sliced host-buffer launch does, and only if a slot fits the LDS the line is built in (very long chromosome names
+// do not; the host then formats every line as before)
+abm::u32 se_text_stride(const abm_ctx *ctx, const LaunchShape &s, abm::u32 cig_stride, bool host_results, bool sliced) {
+  if (!ctx->sam_on || !host_results || !sliced) return 0;
+  const abm::u32 stride = sam_stride_for(ctx, s.eff_len, cig_stride);
+  return stride <= abm::sam_line_room(s.GW, s.tb_extra) ? stride : 0;
+}
+
+// Every workspace se_device needs for n reads of one launch shape.  se_device and abm_ctx_reserve both size through
+// this function, so a reserved context grows no buffer mid-run.  n_slices: of a sliced launch, else 0
+void se_reserve(abm_ctx *ctx, uint64_t n, const LaunchShape &s, uint32_t n_slices, bool host_results, abm::u32 sam_stride) {
+  ctx->packed.reserve(n * 4 * s.W); ctx->lens.reserve(n);
+  ctx->work.reserve(32); ctx->next_read.reserve(64);
+  if (n < (1ull << 32)) {  // (a larger batch is mapped in input order)
+    ctx->order.reserve(n); ctx->cls.reserve(n);
+    if (n_slices) { ctx->slice_id.reserve(n); ctx->slice_left.reserve(n_slices); ctx->slice_hist.reserve(abm::order_sliced_hist_words(n_slices)); }
+    else ctx->class33.reserve(33);
+  }
+  // (few reads outgrow their slot: 150-base reads with sim-like indel rates need 1.5 ops of arena per read beside
+  // their 4-op slots)
+  arena_reserve(ctx, 2 * n, host_results);
+  if (sam_stride) { ctx->h_sam.reserve(static_cast<size_t>(n) * sam_stride); ctx->h_sam_len.reserve(n); }
 }
 
 // The launch for a batch's reads of kLdsReadLen + 1 .. kMaxReadLen bases (map_se_long_kernel): the reads are listed
 // on the device, the list's length is fetched (the one place a device entry point waits for the device -- only when
 // the caller announced such reads through max_len), and the list is mapped in rounds of at most 1024 reads, each
 // packed into encodings of its own and mapped by one wave per CU with per-wave traceback tables in global memory.
-// Results land where the main launch left these reads unmapped.  `a` = the main launch's arguments.
+// Results land where the main launch left these reads unmapped.  `main` = the main launch's arguments.
 void se_long_reads(abm_ctx *ctx, const abm::SeArgs &main, uint64_t n, const char *d_blob, const uint64_t *d_off,
-                   abm::u32 max_len, double valid_frac, hipStream_t st) {
+                   abm::u32 max_len, double valid_frac, HostMode host, hipStream_t st) {
   if (n >= (1ull << 32)) throw std::invalid_argument("batch too large for the long-read launch (>= 2^32 reads)");
   ctx->long_list.reserve(n);
   ctx->long_count.reserve(1);
@@ -366,33 +460,31 @@ void se_long_reads(abm_ctx *ctx, const abm::SeArgs &main, uint64_t n, const char
   abm::u32 count = 0;
   HIPCHK(hipMemcpyAsync(&count, ctx->long_count.p, 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  const abm::u32 W = words_for(max_len), WB = bitwords_for(max_len);
-  const double size_frac = ctx->ix->h.multibit_genome ? 1.0 : valid_frac;
-  const abm::u32 GW = abm::se_window_words(max_len, size_frac);
-  const abm::u32 cap2 = (max_len + 2 + 1) & ~1u;
+  const LaunchShape s = launch_shape(ctx, max_len, valid_frac, ShapeKind::kLong);
+  const abm::u32 cap2 = (s.ctmp_cap + 1) & ~1u;
   int waves = 0;
   if (count) {
-    waves = abm::se_long_resident_waves(W, WB, GW);
+    waves = abm::se_long_resident_waves(s.W, s.WB, s.GW);
     if (waves <= 0) throw HipFail("map_se_long_kernel does not fit on this device (LDS)");
   }
   const abm::u32 round = 1024;
   for (abm::u32 at = 0; at < count; at += round) {
     const abm::u32 m = std::min(round, count - at);
     const abm::u32 grid = std::min<abm::u32>(m, static_cast<abm::u32>(waves));
-    ctx->packed_long.reserve(static_cast<size_t>(m) * 4 * W);
+    ctx->packed_long.reserve(static_cast<size_t>(m) * 4 * s.W);
     ctx->long_tb.reserve(static_cast<size_t>(grid) * abm::se_long_tb_bytes(max_len));
     ctx->long_ctmp.reserve(static_cast<size_t>(grid) * cap2);
-    HIPCHK(abm::launch_pack_listed(d_blob, reinterpret_cast<const abm::u64 *>(d_off), ctx->long_list.p + at, m, W, ctx->packed_long.p, st));
+    HIPCHK(abm::launch_pack_listed(d_blob, reinterpret_cast<const abm::u64 *>(d_off), ctx->long_list.p + at, m, s.W, ctx->packed_long.p, st));
     abm::SeArgs a = main;
     a.packed = ctx->packed_long.p;
     a.order = ctx->long_list.p + at;
     a.n_reads = m;
-    a.W = W; a.WB = WB; a.GW = GW;
+    a.W = s.W; a.WB = s.WB; a.GW = s.GW;
     a.max_len = max_len;
-    a.tb_extra = 0;
-    a.G = 0;
-    a.size_frac = size_frac;
-    a.ctmp_cap = max_len + 2;
+    a.tb_extra = s.tb_extra;
+    a.G = s.G;
+    a.size_frac = s.size_frac;
+    a.ctmp_cap = s.ctmp_cap;
     a.long_tb = ctx->long_tb.p;
     a.long_ctmp = ctx->long_ctmp.p;
     a.long_tb_bytes = abm::se_long_tb_bytes(max_len);
@@ -400,12 +492,10 @@ void se_long_reads(abm_ctx *ctx, const abm::SeArgs &main, uint64_t n, const char
     a.finished = nullptr;
     a.host_tail = nullptr;
     a.read_cycles = nullptr;
-    unsigned long long *counter = ctx->next_read.p + (ctx->launch_seq++ & 63u);
-    HIPCHK(hipMemsetAsync(counter, 0, sizeof(unsigned long long), st));
-    a.next_read = counter;
+    a.next_read = fresh_counter(ctx, st);
     HIPCHK(abm::launch_map_se_long(a, grid, st));
   }
-  if (ctx->host_results) {  // what the main launch's last wave would have published (abm_map_se_batch waits for the stream)
+  if (host.host_results) {  // what the main launch's last wave would have published (abm_map_se_batch waits for the stream)
     HIPCHK(hipMemcpyAsync(&ctx->h_tail.p[0], main.cig_arena_count, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&ctx->h_tail.p[1], main.status, 4, hipMemcpyDeviceToHost, st));
   }
@@ -413,145 +503,92 @@ void se_long_reads(abm_ctx *ctx, const abm::SeArgs &main, uint64_t n, const char
 
 void se_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, const char *d_blob,
                const uint64_t *d_off, uint32_t max_len, abm_hit *d_res, uint32_t *d_cig,
-               uint32_t cig_stride, uint32_t *d_cig_n, uint32_t *d_status, hipStream_t st) {
+               uint32_t cig_stride, uint32_t *d_cig_n, uint32_t *d_status, HostMode host, hipStream_t st) {
   check_params(params);
   if (mode < 0 || mode > 2) throw std::invalid_argument("bad single-end mode");
   if (cig_stride == 0) throw std::invalid_argument("cig_stride must be > 0");
   if (n == 0) return;
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamWaitEvent(st, ctx->last_done, 0));
-  // reads beyond kLdsReadLen bases (rare: long-read libraries) are left out of this launch -- its workspaces, LDS and
-  // filter stay what the batch's ordinary reads need -- and mapped by a launch of their own afterwards (se_long_reads)
+  // reads beyond kLdsReadLen bases (rare: long-read libraries) are mapped by a launch of their own afterwards (se_long_reads)
   const bool has_long = max_len > abm::kLdsReadLen;
-  const abm::u32 eff_len = std::min<abm::u32>(std::max<abm::u32>(max_len, 1), abm::kLdsReadLen);
-  const abm::u32 W = words_for(eff_len), WB = bitwords_for(eff_len);
-  ctx->packed.reserve(n * 4 * W);
-  ctx->lens.reserve(n);
-  ctx->work.reserve(32);
-  HIPCHK(abm::launch_pack_reads(d_blob, reinterpret_cast<const abm::u64 *>(d_off), n, W, ctx->packed.p,
+  const LaunchShape s = launch_shape(ctx, max_len, params->valid_frac, ShapeKind::kSingle);
+  const bool sliced = host.n_slices != 0 && !has_long && n < (1ull << 32);
+  const abm::u32 sam_stride = se_text_stride(ctx, s, cig_stride, host.host_results, sliced);
+  se_reserve(ctx, n, s, sliced ? host.n_slices : 0, host.host_results, sam_stride);
+
+  HIPCHK(abm::launch_pack_reads(d_blob, reinterpret_cast<const abm::u64 *>(d_off), n, s.W, ctx->packed.p,
                                 ctx->lens.p, st));
   abm::SeArgs a{};
   a.ix = current_index(ctx, params->max_candidates ? params->max_candidates : ctx->dix.max_candidates, true);
-  const bool sliced = ctx->sliced_n != 0 && !has_long && n < (1ull << 32);
   if (sliced) {  // (slice boundaries are uploaded by the entry point)
-    ctx->order.reserve(n);
-    ctx->cls.reserve(n);
-    ctx->slice_id.reserve(n);
-    ctx->slice_left.reserve(ctx->sliced_n);
-    ctx->slice_hist.reserve(abm::order_sliced_hist_words(ctx->sliced_n));
-    HIPCHK(abm::launch_order_reads_sliced(a.ix, ctx->packed.p, ctx->lens.p, n, W, mode, ctx->cls.p, ctx->slice_first_d.p,
-                                          ctx->sliced_n, ctx->slice_id.p, ctx->slice_hist.p, ctx->slice_left.p, ctx->order.p, st));
+    HIPCHK(abm::launch_order_reads_sliced(a.ix, ctx->packed.p, ctx->lens.p, n, s.W, mode, ctx->cls.p, ctx->slice_first_d.p,
+                                          host.n_slices, ctx->slice_id.p, ctx->slice_hist.p, ctx->slice_left.p, ctx->order.p, st));
     a.order = ctx->order.p;
     a.slice_id = ctx->slice_id.p;
     a.slice_left = ctx->slice_left.p;
     a.slice_done = ctx->h_slice_done.p;
   }
   else if (n < (1ull << 32)) {
-    ctx->order.reserve(n);
-    ctx->cls.reserve(n);
-    ctx->class33.reserve(33);
-    HIPCHK(abm::launch_order_reads(a.ix, ctx->packed.p, ctx->lens.p, n, W, mode, ctx->cls.p, ctx->class33.p,
+    HIPCHK(abm::launch_order_reads(a.ix, ctx->packed.p, ctx->lens.p, n, s.W, mode, ctx->cls.p, ctx->class33.p,
                                    ctx->order.p, st));
     a.order = ctx->order.p;
   }
   a.packed = ctx->packed.p;
   a.lens = ctx->lens.p;
   a.n_reads = n;
-  a.W = W;
-  a.WB = WB;
-  a.max_len = eff_len;
-  // IUPAC genome letters can drive a Hamming sum below zero, which the reference turns into the
-  // widest band (61); size the LDS for it only when such letters exist
-  const double size_frac = ctx->ix->h.multibit_genome ? 1.0 : params->valid_frac;
-  a.size_frac = size_frac;
-  a.GW = abm::se_window_words(eff_len, size_frac);
-  a.tb_extra = abm::tb_extra_bytes(a.GW, eff_len, size_frac);
-  // cooperative window loads from the genome's bit planes (hamming_planes): not for genomes with IUPAC letters (no
-  // planes; their admission rule needs full_compare's word-by-word running sums) nor for reads beyond 448 bases; ABM_COOP_WINDOWS=0 switches them off (experiments)
-  // (G lanes x 64 bases cover a window of eff_len + 63 bases)
-  a.G = a.ix.planes[0] == nullptr ? 0u : (eff_len <= 2 * abm::kPlaneBlock ? 2u : (eff_len <= 4 * abm::kPlaneBlock - 64 ? 4u : (eff_len <= 8 * abm::kPlaneBlock - 64 ? 8u : 0u)));
-  if (const char *e = experiment_env("ABM_COOP_WINDOWS")) { if (e[0] == '0') a.G = 0; else if (e[0] == '4' && a.G == 2) a.G = 4; }
+  a.W = s.W; a.WB = s.WB; a.GW = s.GW;
+  a.max_len = s.eff_len;
+  a.size_frac = s.size_frac;
+  a.tb_extra = s.tb_extra;
+  a.G = s.G;
+  a.ctmp_cap = s.ctmp_cap;
   a.mode = mode;
   a.valid_frac = params->valid_frac;
   a.res = reinterpret_cast<abm::Hit *>(d_res);
   a.cig = d_cig;
   a.cig_stride = cig_stride;
-  a.ctmp_cap = eff_len + 2;
-  {  // arena for the CIGARs that outgrow their slot: few reads do, one op per read is ample
-    // (150-base reads with sim-like indel rates need 1.5 ops of arena per read beside their 4-op slots; an arena that
-    // overflows costs a second mapping of the batch)
-    const size_t want = std::max<size_t>(ctx->arena_want, std::max<size_t>(1u << 16, 2 * n));
-    ctx->cig_arena_count.reserve(1);
-    HIPCHK(hipMemsetAsync(ctx->cig_arena_count.p, 0, 4, st));
-    a.cig_arena_count = ctx->cig_arena_count.p;
-    if (ctx->host_results) {  // (abm_map_se_batch: the arena lies in pinned host memory, like the rest of its results)
-      ctx->h_arena.reserve(std::min<size_t>(want, 0xFFFFFF00u));
-      ctx->h_tail.reserve(2);
-      ctx->finished.reserve(1);
-      HIPCHK(hipMemsetAsync(ctx->finished.p, 0, 4, st));
-      ctx->h_tail.p[0] = ctx->h_tail.p[1] = 0;
-      a.cig_arena = ctx->h_arena.p;
-      a.cig_arena_cap = static_cast<abm::u32>(std::min<size_t>(ctx->h_arena.cap, 0xFFFFFF00u));
-      a.finished = ctx->finished.p;
-      a.host_tail = has_long ? nullptr : ctx->h_tail.p;  // (with a long-read launch to follow, the summary words are copied out after it)
-    }
-    else {
-      ctx->cig_arena.reserve(std::min<size_t>(want, 0xFFFFFF00u));
-      a.cig_arena = ctx->cig_arena.p;
-      a.cig_arena_cap = static_cast<abm::u32>(std::min<size_t>(ctx->cig_arena.cap, 0xFFFFFF00u));
-    }
-  }
   a.cig_n = d_cig_n;
   a.status = d_status;
   a.work = ctx->work.p;
   a.blob = d_blob;
   a.off = reinterpret_cast<const abm::u64 *>(d_off);
-  ctx->sam_stride = 0;
+  a.read_cycles = ctx->phase_stamps ? ctx->read_cycles : nullptr;
+  arena_setup(ctx, a, host.host_results, st);
+  if (host.host_results) {
+    HIPCHK(hipMemsetAsync(ctx->finished.p, 0, 4, st));
+    a.finished = ctx->finished.p;
+    a.host_tail = has_long ? nullptr : ctx->h_tail.p;  // (with a long-read launch to follow, the summary words are copied out after it)
+  }
+  // the kernel writes every read's SAM text (after QNAME) next to its hit; a line that does not fit its slot is
+  // formatted by the host as before
+  ctx->sam_stride = sam_stride;
   ctx->pe_sam_stride = 0;  // (the buffers are shared with the paired-end text)
-  if (ctx->sam_on && ctx->host_results && sliced && sam_stride_for(ctx, eff_len, cig_stride) <= abm::sam_line_room(a.GW, a.tb_extra)) {
-    // the kernel writes every read's SAM text (after QNAME) next to its hit; a line that does not fit its slot is formatted
-    // by the host as before.  (A slot longer than the LDS the line is built in -- very long chromosome names -- and the
-    // launch writes no text.)
-    const abm::u32 stride = sam_stride_for(ctx, eff_len, cig_stride);
-    ctx->h_sam.reserve(static_cast<size_t>(n) * stride);
-    ctx->h_sam_len.reserve(n);
+  if (sam_stride) {
     a.sam_tail = ctx->h_sam.p;
     a.sam_len = ctx->h_sam_len.p;
-    a.sam_stride = stride;
+    a.sam_stride = sam_stride;
     a.sam_allow_ambig = ctx->sam_allow_ambig;
-    ctx->sam_stride = stride;
   }
-  // a small ring of work counters so launches queued on different streams never share one
-  ctx->next_read.reserve(64);
-  auto fresh_counter = [&](hipStream_t on) {
-    unsigned long long *counter = ctx->next_read.p + (ctx->launch_seq++ & 63u);
-    HIPCHK(hipMemsetAsync(counter, 0, sizeof(unsigned long long), on));
-    return counter;
-  };
-  a.read_cycles = ctx->phase_stamps ? ctx->read_cycles : nullptr;
   // the occupancy query costs milliseconds: remember it per launch shape
-  const uint64_t shape = (static_cast<uint64_t>(W) << 48) ^ (static_cast<uint64_t>(eff_len) << 8) ^ static_cast<uint64_t>(size_frac * 255.0);
+  const uint64_t key = (static_cast<uint64_t>(s.W) << 48) ^ (static_cast<uint64_t>(s.eff_len) << 8) ^ static_cast<uint64_t>(s.size_frac * 255.0);
   int waves;
-  auto it = ctx->se_waves.find(shape);
+  auto it = ctx->se_waves.find(key);
   if (it != ctx->se_waves.end()) waves = it->second;
-  else { waves = abm::se_resident_waves(W, WB, a.ctmp_cap, eff_len, size_frac); ctx->se_waves[shape] = waves; }
+  else { waves = abm::se_resident_waves(s.W, s.WB, s.ctmp_cap, s.eff_len, s.size_frac); ctx->se_waves[key] = waves; }
   if (waves <= 0) throw HipFail("map_se_kernel does not fit on this device (LDS/occupancy)");
   abm::u32 grid = static_cast<abm::u32>(waves);  // persistent: one wave per resident slot
   if (const char *e = experiment_env("ABM_GRID_WAVES")) grid = std::max(64, std::atoi(e));
 
-  const hipEvent_t e1 = begin_timed(ctx, st);
-  a.next_read = fresh_counter(st);
-  a.drained = ctx->signal_drained ? ctx->drained : nullptr;
-  HIPCHK(abm::launch_map_se(a, eff_len, grid, ctx->phase_stamps, st));
-  if (e1) HIPCHK(hipEventRecord(e1, st));
-  if (has_long) se_long_reads(ctx, a, n, d_blob, d_off, std::min<abm::u32>(max_len, abm::kMaxReadLen), params->valid_frac, st);
+  a.drained = host.signal_drained ? ctx->drained : nullptr;
+  timed_launch(ctx, st, [&] {
+    a.next_read = fresh_counter(ctx, st);
+    HIPCHK(abm::launch_map_se(a, s.eff_len, grid, ctx->phase_stamps, st));
+  });
+  if (has_long) se_long_reads(ctx, a, n, d_blob, d_off, std::min<abm::u32>(max_len, abm::kMaxReadLen), params->valid_frac, host, st);
   HIPCHK(hipEventRecord(ctx->last_done, st));
 }
 
-// CIGARs as the kernels leave them -- `stride` ops per read in fixed slots, longer ones whole in the launch's
-// arena with slot[0] = where -- into the caller's compact blob + n + 1 offsets, in read order.  Host-side on
-// purpose: no kernel has to run after the mapping kernel, so a batch's results leave the GPU while the next
-// batch's (persistent, device-filling) mapping kernel is already running.
 // fn(lo, hi) over [0, n) on a few host threads (the batch entry points' passes over per-read arrays: with 8 M reads
 // per batch a single-threaded pass costs tens of ms -- hundreds while the CLI's parser threads own the memory bus)
 template <class F> void parallel_ranges(uint64_t n, F &&fn) {
@@ -600,11 +637,35 @@ OffsetScan scan_offsets(const uint64_t *seq_off, uint64_t n, HostBuf<uint64_t> &
 // ops per CIGAR slot of the paired-end host entry point (longer CIGARs go to the arena): 150-base ends with sim-like
 // indel rates have more than 4 ops a quarter of the time, more than 8 one time in fifty
 constexpr uint32_t kPeHostSlotOps = 8;
+// ... and of the single-end ones: four ops cover nearly every read
+constexpr uint32_t kSeHostSlotOps = 4;
+
+// Staging of the host-buffer entry points for n reads (pairs) with `bytes` of sequence: the batch on the device, and
+// its hits, op counts and CIGAR slots in pinned memory, where the kernels write them
+void se_staging_reserve(abm_ctx *ctx, uint64_t n, uint64_t bytes) {
+  ctx->blob.reserve(std::max<uint64_t>(bytes, 1)); ctx->off.reserve(n + 1); ctx->status.reserve(1);
+  ctx->h_res.reserve(n); ctx->h_cn.reserve(n); ctx->h_slots.reserve(n * kSeHostSlotOps);
+}
+void slice_staging_reserve(abm_ctx *ctx, uint32_t n_slices) {  // slice boundaries (host, device), a completion word per slice
+  ctx->h_slice_first.reserve(n_slices + 1); ctx->slice_first_d.reserve(n_slices + 1); ctx->h_slice_done.reserve(n_slices);
+}
+void pe_staging_reserve(abm_ctx *ctx, uint64_t n, uint64_t bytes1, uint64_t bytes2) {
+  ctx->blob.reserve(std::max<uint64_t>(bytes1, 1)); ctx->blob2.reserve(std::max<uint64_t>(bytes2, 1));
+  ctx->off.reserve(n + 1); ctx->off2.reserve(n + 1); ctx->status.reserve(1);
+  ctx->h_pe_out.reserve(n * 5);  // 20 B pairs + 8 B + 8 B, in units of 8 B
+  ctx->h_cn.reserve(n); ctx->h_cn2.reserve(n);
+  ctx->h_slots.reserve(n * kPeHostSlotOps); ctx->h_slots2.reserve(n * kPeHostSlotOps);
+}
+
+// CIGARs as the kernels leave them -- `stride` ops per read in fixed slots, longer ones whole in the launch's
+// arena with slot[0] = where -- into the caller's compact blob + n + 1 offsets, in read order.  Host-side on
+// purpose: no kernel has to run after the mapping kernel, so a batch's results leave the GPU while the next
+// batch's (persistent, device-filling) mapping kernel is already running.
 void assemble_cigars(uint64_t n, uint32_t stride, const uint32_t *cn, const uint32_t *slots, const uint32_t *arena,
                      uint64_t arena_n, uint32_t *out_blob, uint64_t cap, uint64_t *out_off) {
   out_off[0] = 0;
   for (uint64_t i = 0; i < n; ++i) out_off[i + 1] = out_off[i] + cn[i];
-  if (out_off[n] > cap) throw std::length_error("cig_capacity too small");
+  if (out_off[n] > cap || (out_off[n] && !out_blob)) throw std::length_error("cig_capacity too small");
   auto fill = [&](uint64_t lo, uint64_t hi) {
     for (uint64_t i = lo; i < hi; ++i) {
       const uint32_t k = cn[i];
@@ -629,15 +690,106 @@ void pe_tier2_reserve(abm_ctx *ctx, size_t waves) {
   ctx->heap2.reserve(waves * cap);
   ctx->log2.reserve(waves * (32 + 12 * cap));
 }
-// waves a tier-2 launch for reads of up to max_len bases can keep resident (what pe_device computes per call)
-int pe_tier2_waves(abm_ctx *ctx, abm::u32 max_len, double valid_frac) {
-  const abm::u32 eff_len = std::min<abm::u32>(std::max<abm::u32>(max_len, 1), abm::kLdsReadLen);
-  const abm::u32 W = (eff_len + 15) / 16, WB = (eff_len + 63) / 64 + 1;
-  const double size_frac = ctx->ix->h.multibit_genome ? 1.0 : valid_frac;
-  const abm::u32 GW = abm::se_window_words(eff_len, size_frac);
-  const bool coop = ctx->dix.planes[0] != nullptr && eff_len <= 8 * abm::kPlaneBlock - 64;
-  const size_t lds = abm::pe_lds_bytes(W, WB, GW, eff_len + 2, eff_len, size_frac, abm::kPeCapLarge, true);
-  return abm::pe_resident_waves(lds, true, abm::pe_waves_per_simd(lds, false, coop));
+
+// A launch of the whole-pair kernel (map_pe_kernel) for n pairs: tier 1 unsplit (small sets in LDS) or tier 2 (`large`:
+// sets of kPeCapLarge entries per wave in global memory); text = the launch writes SAM records
+struct PeLaunch { size_t lds; int wps, waves; };
+PeLaunch pe_whole_launch(const abm_ctx *ctx, const LaunchShape &s, uint64_t n, bool large, bool text) {
+  PeLaunch l{};
+  l.lds = abm::pe_lds_bytes(s.W, s.WB, s.GW, s.ctmp_cap, s.eff_len, s.size_frac, large ? abm::kPeCapLarge : abm::kPeTier1Cap, large) + (text ? abm::kPeFinBytes : 0);
+  l.wps = abm::pe_waves_per_simd(l.lds, ctx->phase_stamps, s.G != 0);
+  if (const char *e = experiment_env(large ? "ABM_PE_WPS2" : "ABM_PE_WPS")) { if (!ctx->phase_stamps && s.G != 0 && (e[0] == '3' || e[0] == '4')) l.wps = e[0] - '0'; }
+  if (text) l.wps = abm::pe_text_waves_per_simd();  // (the text builds: launch_map_pe)
+  l.waves = abm::pe_resident_waves(l.lds, large, l.wps);
+  // (tier 2: no more waves than the batch has pairs: every wave owns 2.3 MB of lists, heap and log in global memory -- 7.6 GB
+  // for a full grid -- which a batch of a few thousand pairs, or the 32 contexts of two replicas on one device, must not ask for)
+  if (large && l.waves > 0) l.waves = static_cast<int>(std::min<uint64_t>(static_cast<uint64_t>(l.waves), std::max<uint64_t>(n, 64)));
+  return l;
+}
+
+// tier 1 split by phase (the default; 0: tier 1 as ONE kernel per pair, as in rounds 1-4 -- same-box comparisons)
+bool pe_split_on(const abm_ctx *ctx) {
+  if (const char *e = experiment_env("ABM_PE_SPLIT")) return e[0] != '0';
+  return ctx->pe_split != 0;
+}
+// entries a list may grow to in the seed kernel (beyond kPeTier1Cap: in its staging area)
+abm::u32 pe_seed_cap(const abm_ctx *ctx) {
+  abm::u32 scap = ctx->pe_scap ? ctx->pe_scap : abm::kPeTier1Cap;
+  if (const char *e = experiment_env("ABM_PE_SCAP")) scap = static_cast<abm::u32>(std::atoi(e));
+  return std::min<abm::u32>(16384, std::max<abm::u32>(abm::kPeTier1Cap, scap));
+}
+// entries of the hand-over area for n pairs (a list that finds no room sends its pair to the whole-pair kernel)
+size_t pe_hand_entries(const abm_ctx *ctx, uint64_t n) {
+  // (abm_ctx_set_pe_split's hand_entries, when given, is taken as it is: tests run the area out of room with it)
+  if (ctx->hand_want) return std::max<size_t>(ctx->hand_want, 64);
+  size_t per_pair = pe_seed_cap(ctx) > abm::kPeTier1Cap ? 256 : 64;
+  if (const char *e = experiment_env("ABM_PE_HAND_PER_PAIR")) per_pair = static_cast<size_t>(std::max(4, std::atoi(e)));
+  return std::min<size_t>(std::max<size_t>(n * per_pair, size_t(1) << 16), 0xFFFFFF00u);
+}
+// the seed kernel's launch: LDS per wave and its grid (0: it does not fit)
+struct PeSeedLaunch { size_t lds; abm::u32 grid; };
+PeSeedLaunch pe_seed_launch(const LaunchShape &s, uint64_t n) {
+  PeSeedLaunch l{};
+  l.lds = abm::pe_seed_lds_bytes(s.W, s.WB, s.eff_len, abm::kPeTier1Cap);
+  const int waves = abm::pe_seed_resident_waves(l.lds, s.G != 0);
+  l.grid = waves <= 0 ? 0u : static_cast<abm::u32>(std::min<uint64_t>(n, waves));
+  return l;
+}
+
+// Bytes of one end's SAM-text slot if the launches that finish pairs write both ends' records themselves
+// (abm_ctx_set_sam_tails, format_pe_tails), else 0: their builds on the bit planes only, not the diagnostic ones, and
+// only if a line's slot fits the LDS it is built in; otherwise the batch has no text and the host formats it all
+abm::u32 pe_text_stride(const abm_ctx *ctx, const LaunchShape &s, abm::u32 cig_stride, bool host_results) {
+  if (!ctx->sam_on || !host_results || ctx->phase_stamps || s.G == 0) return 0;
+  const abm::u32 stride = pe_sam_stride_for(ctx, s.eff_len, cig_stride);
+  return stride <= abm::sam_line_room(s.GW, s.tb_extra) ? stride : 0;
+}
+
+// What pe_device settles before it touches a buffer: the route through tier 1 (split by phase or not), the text slot, and the
+// launches whose resident waves size workspaces (each costs an occupancy query, so they are settled once per call)
+struct PePlan {
+  bool split;
+  abm::u32 sam_stride, scap;
+  PeLaunch t1;        // tier 1 unsplit (only when !split)
+  PeSeedLaunch seed;  // the seed kernel (only when split)
+  PeLaunch t2;
+};
+PePlan pe_plan(const abm_ctx *ctx, uint64_t n, const LaunchShape &s, abm::u32 cig_stride, bool host_results) {
+  PePlan p{};
+  p.split = pe_split_on(ctx);
+  p.sam_stride = pe_text_stride(ctx, s, cig_stride, host_results);
+  p.scap = pe_seed_cap(ctx);
+  if (p.split) p.seed = pe_seed_launch(s, n);
+  else p.t1 = pe_whole_launch(ctx, s, n, false, p.sam_stride != 0);
+  p.t2 = pe_whole_launch(ctx, s, n, true, p.sam_stride != 0);
+  return p;
+}
+
+// Every workspace pe_device needs for n pairs of one launch shape, with the context's split settings as they stand.
+// pe_device and abm_ctx_reserve both size through this function: growing a buffer mid-run frees the old one, and hipFree
+// waits for the whole device -- the split's first end-to-end run lost half its rate to exactly that
+// (profiles/r05_pe_e2e_regrowth.log).  mode_slots: lists per pair (8 in the random-PBAT mode, else 4)
+void pe_reserve(abm_ctx *ctx, uint64_t n, const LaunchShape &s, abm::u32 mode_slots, bool host_results, const PePlan &p) {
+  ctx->packed.reserve(n * 4 * s.W); ctx->packed2.reserve(n * 4 * s.W); ctx->lens.reserve(n); ctx->lens2.reserve(n);
+  ctx->work.reserve(32); ctx->next_read.reserve(64);
+  ctx->order.reserve(n); ctx->cls.reserve(n); ctx->class33.reserve(33);
+  ctx->need_big.reserve(n); ctx->subset.reserve(n); ctx->subset_count.reserve(1);
+  if (p.sam_stride) { ctx->h_sam.reserve(static_cast<size_t>(2 * n) * p.sam_stride); ctx->h_sam_len.reserve(2 * n); ctx->h_pe_kind.reserve(n); }
+  // (two ends, and sim-like 150-base reads carry two or more indels a quarter of the time: 2 n ops overflowed, and an
+  // overflowing arena means the whole batch is mapped AGAIN with a larger one -- with 8 contexts per GPU half of an
+  // end-to-end run's batches were, profiles/r04_pe_e2e_variants_arena.log)
+  arena_reserve(ctx, 4 * n, host_results);
+  if (!p.split) ctx->payload1.reserve(static_cast<size_t>(std::max(p.t1.waves, 0)) * abm::kPeTier1Cap);
+  else {
+    // the phase split's hand-over area: list headers per pair, the lists' entries, the bump counter; the seed kernel's
+    // per-wave staging area; the second route's pair list
+    const size_t hand_cap = pe_hand_entries(ctx, n), stage = p.scap > abm::kPeTier1Cap ? static_cast<size_t>(p.seed.grid) * p.scap : 0;
+    ctx->hand_hdr.reserve(n * mode_slots * 2); ctx->hand_count.reserve(1);
+    ctx->hand_pos.reserve(hand_cap); ctx->hand_d.reserve(hand_cap);
+    ctx->stage_pos.reserve(stage); ctx->stage_d.reserve(stage);
+    ctx->subset_b.reserve(n); ctx->subset_count_b.reserve(1); ctx->class33_b.reserve(33);
+  }
+  pe_tier2_reserve(ctx, static_cast<size_t>(std::max(p.t2.waves, 0)));
 }
 
 // The launch for a batch's pairs with an end of kLdsReadLen + 1 .. kMaxReadLen bases (map_pe_kernel<.., LONG>), after
@@ -655,40 +807,34 @@ void pe_long_pairs(abm_ctx *ctx, const abm::PeArgs &main, uint64_t n, const char
   HIPCHK(hipMemcpyAsync(&count, ctx->long_count.p, 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   if (count == 0) return;
-  const abm::u32 W = words_for(max_len), WB = bitwords_for(max_len);
-  const double size_frac = ctx->ix->h.multibit_genome ? 1.0 : valid_frac;
-  const abm::u32 GW = abm::se_window_words(max_len, size_frac);
-  const abm::u32 cap2 = (max_len + 2 + 1) & ~1u;
-  const int waves = abm::pe_long_resident_waves(GW);
+  const LaunchShape s = launch_shape(ctx, max_len, valid_frac, ShapeKind::kLong);
+  const abm::u32 cap2 = (s.ctmp_cap + 1) & ~1u;
+  const int waves = abm::pe_long_resident_waves(s.GW);
   if (waves <= 0) throw HipFail("the paired-end long-end launch does not fit on this device (LDS)");
   const abm::u32 round = 256;  // (a round's packed encodings: 2 x 256 x 4 W words = 32 MB at the longest reads)
   for (abm::u32 at = 0; at < count; at += round) {
     const abm::u32 m = std::min(round, count - at);
     const abm::u32 grid = std::min<abm::u32>(m, static_cast<abm::u32>(waves));
-    const size_t cap = abm::kPeCapLarge;
-    ctx->packed_long.reserve(static_cast<size_t>(m) * 4 * W);
-    ctx->packed_long2.reserve(static_cast<size_t>(m) * 4 * W);
-    ctx->long_q.reserve(static_cast<size_t>(grid) * abm::pe_long_q_words(W, WB));
+    ctx->packed_long.reserve(static_cast<size_t>(m) * 4 * s.W);
+    ctx->packed_long2.reserve(static_cast<size_t>(m) * 4 * s.W);
+    ctx->long_q.reserve(static_cast<size_t>(grid) * abm::pe_long_q_words(s.W, s.WB));
     ctx->long_tb.reserve(static_cast<size_t>(grid) * abm::se_long_tb_bytes(max_len));
     ctx->long_ctmp.reserve(static_cast<size_t>(grid) * cap2);
-    ctx->payload2.reserve(static_cast<size_t>(grid) * cap);
-    ctx->list2.reserve(static_cast<size_t>(grid) * 4 * cap);
-    ctx->heap2.reserve(static_cast<size_t>(grid) * cap);
-    ctx->log2.reserve(static_cast<size_t>(grid) * (32 + 12 * cap));
-    HIPCHK(abm::launch_pack_listed(d_blob1, reinterpret_cast<const abm::u64 *>(d_off1), ctx->long_list.p + at, m, W, ctx->packed_long.p, st));
-    HIPCHK(abm::launch_pack_listed(d_blob2, reinterpret_cast<const abm::u64 *>(d_off2), ctx->long_list.p + at, m, W, ctx->packed_long2.p, st));
+    pe_tier2_reserve(ctx, grid);
+    HIPCHK(abm::launch_pack_listed(d_blob1, reinterpret_cast<const abm::u64 *>(d_off1), ctx->long_list.p + at, m, s.W, ctx->packed_long.p, st));
+    HIPCHK(abm::launch_pack_listed(d_blob2, reinterpret_cast<const abm::u64 *>(d_off2), ctx->long_list.p + at, m, s.W, ctx->packed_long2.p, st));
     abm::PeArgs a = main;
     a.packed1 = ctx->packed_long.p; a.packed2 = ctx->packed_long2.p;
     a.order = nullptr;
     a.subset = ctx->long_list.p + at;
     HIPCHK(hipMemcpyAsync(ctx->long_count.p + 1, &m, 4, hipMemcpyHostToDevice, st));  // (pageable source: copied before the call returns)
     a.subset_count = ctx->long_count.p + 1;
-    a.W = W; a.WB = WB; a.GW = GW;
+    a.W = s.W; a.WB = s.WB; a.GW = s.GW;
     a.max_len = max_len;
-    a.tb_extra = 0;
-    a.G = 0;
-    a.ctmp_cap = max_len + 2;
-    a.cap = static_cast<abm::u32>(cap);
+    a.tb_extra = s.tb_extra;
+    a.G = s.G;
+    a.ctmp_cap = s.ctmp_cap;
+    a.cap = abm::kPeCapLarge;
     a.log_ws = ctx->log2.p; a.heap_ws = ctx->heap2.p; a.payload_ws = ctx->payload2.p; a.list_ws = ctx->list2.p;
     a.long_q = ctx->long_q.p;
     a.long_tb = ctx->long_tb.p;
@@ -696,9 +842,7 @@ void pe_long_pairs(abm_ctx *ctx, const abm::PeArgs &main, uint64_t n, const char
     a.long_tb_bytes = abm::se_long_tb_bytes(max_len);
     a.pair_diag = nullptr;
     a.pair_phases = nullptr;
-    unsigned long long *counter = ctx->next_read.p + (ctx->launch_seq++ & 63u);
-    HIPCHK(hipMemsetAsync(counter, 0, sizeof(unsigned long long), st));
-    a.next_read = counter;
+    a.next_read = fresh_counter(ctx, st);
     HIPCHK(abm::launch_map_pe_long(a, grid, st));
     HIPCHK(hipStreamSynchronize(st));  // (the next round reuses the packed encodings and the count word)
   }
@@ -707,7 +851,7 @@ void pe_long_pairs(abm_ctx *ctx, const abm::PeArgs &main, uint64_t n, const char
 void pe_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, const char *d_blob1,
                const uint64_t *d_off1, const char *d_blob2, const uint64_t *d_off2, uint32_t max_len,
                abm_pair *d_pair, abm_hit *d_se1, abm_hit *d_se2, uint32_t *d_cig1, uint32_t *d_cig2,
-               uint32_t cig_stride, uint32_t *d_cig_n1, uint32_t *d_cig_n2, uint32_t *d_status, hipStream_t st) {
+               uint32_t cig_stride, uint32_t *d_cig_n1, uint32_t *d_cig_n2, uint32_t *d_status, HostMode host, hipStream_t st) {
   check_params(params);
   if (mode < 0 || mode > 2) throw std::invalid_argument("bad paired-end mode");
   if (cig_stride == 0) throw std::invalid_argument("cig_stride must be > 0");
@@ -715,198 +859,103 @@ void pe_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
   if (n >= (1ull << 32)) throw std::invalid_argument("batch too large (>= 2^32 pairs)");
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamWaitEvent(st, ctx->last_done, 0));
-  const abm::u32 eff_len = std::min<abm::u32>(std::max<abm::u32>(max_len, 1), abm::kLdsReadLen);  // (pairs: no long-read launch)
-  const abm::u32 W = words_for(eff_len), WB = bitwords_for(eff_len);
-  ctx->packed.reserve(n * 4 * W);
-  ctx->packed2.reserve(n * 4 * W);
-  ctx->lens.reserve(n);
-  ctx->lens2.reserve(n);
-  ctx->work.reserve(32);
-  ctx->order.reserve(n);
-  ctx->cls.reserve(n);
-  ctx->class33.reserve(33);
-  ctx->need_big.reserve(n);
-  ctx->subset.reserve(n);
-  ctx->subset_count.reserve(1);
-  ctx->next_read.reserve(64);
-  HIPCHK(abm::launch_pack_reads(d_blob1, reinterpret_cast<const abm::u64 *>(d_off1), n, W, ctx->packed.p, ctx->lens.p, st));
-  HIPCHK(abm::launch_pack_reads(d_blob2, reinterpret_cast<const abm::u64 *>(d_off2), n, W, ctx->packed2.p, ctx->lens2.p, st));
+  // (ends beyond kLdsReadLen bases: tiers 1 and 2 treat such a pair as empty; pe_long_pairs maps it afterwards)
+  const bool has_long = max_len > abm::kLdsReadLen;
+  const LaunchShape s = launch_shape(ctx, max_len, params->valid_frac, ShapeKind::kPair);
+  const PePlan p = pe_plan(ctx, n, s, cig_stride, host.host_results);
+  const bool text = p.sam_stride != 0, split = p.split;
+  pe_reserve(ctx, n, s, mode == 2 ? 8u : 4u, host.host_results, p);
+
+  HIPCHK(abm::launch_pack_reads(d_blob1, reinterpret_cast<const abm::u64 *>(d_off1), n, s.W, ctx->packed.p, ctx->lens.p, st));
+  HIPCHK(abm::launch_pack_reads(d_blob2, reinterpret_cast<const abm::u64 *>(d_off2), n, s.W, ctx->packed2.p, ctx->lens2.p, st));
   abm::PeArgs a{};
   a.ix = current_index(ctx, params->max_candidates ? params->max_candidates : ctx->dix.max_candidates, false);
-  HIPCHK(abm::launch_order_reads(a.ix, ctx->packed.p, ctx->lens.p, n, W, mode == 1 ? 1 : 0, ctx->cls.p, ctx->class33.p,
+  HIPCHK(abm::launch_order_reads(a.ix, ctx->packed.p, ctx->lens.p, n, s.W, mode == 1 ? 1 : 0, ctx->cls.p, ctx->class33.p,
                                  ctx->order.p, st));
   a.packed1 = ctx->packed.p; a.packed2 = ctx->packed2.p;
   a.lens1 = ctx->lens.p; a.lens2 = ctx->lens2.p;
   a.order = ctx->order.p;
   a.subset = ctx->subset.p; a.subset_count = ctx->subset_count.p;
   a.n_pairs = n;
-  const double size_frac = ctx->ix->h.multibit_genome ? 1.0 : std::max(params->valid_frac, params->valid_frac);
-  a.W = W; a.WB = WB; a.max_len = eff_len; a.GW = abm::se_window_words(eff_len, size_frac);
-  a.tb_extra = abm::tb_extra_bytes(a.GW, eff_len, size_frac);
-  // cooperative window loads from the bit planes, as in the single-end path (see there)
-  a.G = a.ix.planes[0] == nullptr ? 0u : (eff_len <= 4 * abm::kPlaneBlock - 64 ? 4u : (eff_len <= 8 * abm::kPlaneBlock - 64 ? 8u : 0u));
-  if (const char *e = experiment_env("ABM_COOP_WINDOWS")) if (e[0] == '0') a.G = 0;
+  a.W = s.W; a.WB = s.WB; a.max_len = s.eff_len; a.GW = s.GW;
+  a.tb_extra = s.tb_extra;
+  a.G = s.G;
+  a.ctmp_cap = s.ctmp_cap;
   a.mode = mode;
   a.valid_frac = params->valid_frac;
   a.min_frag = params->min_frag; a.max_frag = params->max_frag;
   a.allow_ambig = params->allow_ambig;
   a.pairs = reinterpret_cast<abm::Hit *>(d_pair);
   a.se1 = reinterpret_cast<abm::Hit *>(d_se1); a.se2 = reinterpret_cast<abm::Hit *>(d_se2);
-  // SAM text (abm_ctx_set_sam_tails): the launches that finish pairs write both ends' records after QNAME into pinned
-  // memory (format_pe_tails).  Their builds on the bit planes only, not the diagnostic ones, and only if a line's slot
-  // fits the LDS it is built in; otherwise the batch has no text and the host formats it all.
-  ctx->sam_stride = 0;
-  ctx->pe_sam_stride = 0;
-  bool text = false;
-  if (ctx->sam_on && ctx->host_results && !ctx->phase_stamps && a.G != 0) {
-    const abm::u32 stride = pe_sam_stride_for(ctx, eff_len, cig_stride);
-    if (stride <= abm::sam_line_room(a.GW, a.tb_extra)) {
-      ctx->h_sam.reserve(static_cast<size_t>(2 * n) * stride);
-      ctx->h_sam_len.reserve(2 * n);
-      ctx->h_pe_kind.reserve(n);
-      std::memset(ctx->h_pe_kind.p, abm::kPeTextHost, n);  // (a pair no launch finished stays the host's)
-      std::memset(ctx->h_sam_len.p, 0, 2 * n * sizeof(abm::u32));
-      a.blob1 = d_blob1; a.off1 = reinterpret_cast<const abm::u64 *>(d_off1);
-      a.blob2 = d_blob2; a.off2 = reinterpret_cast<const abm::u64 *>(d_off2);
-      a.sam_tail = ctx->h_sam.p;
-      a.sam_len = ctx->h_sam_len.p;
-      a.sam_kind = ctx->h_pe_kind.p;
-      a.sam_stride = stride;
-      a.sam_allow_ambig = ctx->sam_allow_ambig;
-      ctx->pe_sam_stride = stride;
-      ctx->pe_sam_pairs = n;
-      text = true;
-    }
-  }
-  const size_t fin_lds = text ? abm::kPeFinBytes : 0;
   a.cig1 = d_cig1; a.cig2 = d_cig2; a.cig_stride = cig_stride; a.cig_n1 = d_cig_n1; a.cig_n2 = d_cig_n2;
-  a.ctmp_cap = eff_len + 2;
-  const bool has_long = max_len > abm::kLdsReadLen;
-  {
-    // (two ends, and sim-like 150-base reads carry two or more indels a quarter of the time: 2 n ops overflowed, and an
-    // overflowing arena means the whole batch is mapped AGAIN with a larger one -- with 8 contexts per GPU half of an
-    // end-to-end run's batches were, profiles/r04_pe_e2e_variants_arena.log)
-    const size_t want = std::max<size_t>(ctx->arena_want, std::max<size_t>(1u << 16, 4 * n));
-    ctx->cig_arena_count.reserve(1);
-    HIPCHK(hipMemsetAsync(ctx->cig_arena_count.p, 0, 4, st));
-    a.cig_arena_count = ctx->cig_arena_count.p;
-    if (ctx->host_results) {  // (abm_map_pe_batch: the arena lies in pinned host memory, like the rest of its results)
-      ctx->h_arena.reserve(std::min<size_t>(want, 0xFFFFFF00u));
-      ctx->h_tail.reserve(2);
-      ctx->finished.reserve(1);
-      ctx->h_tail.p[0] = ctx->h_tail.p[1] = 0;
-      a.cig_arena = ctx->h_arena.p;
-      a.cig_arena_cap = static_cast<abm::u32>(std::min<size_t>(ctx->h_arena.cap, 0xFFFFFF00u));
-    }
-    else {
-      ctx->cig_arena.reserve(std::min<size_t>(want, 0xFFFFFF00u));
-      a.cig_arena = ctx->cig_arena.p;
-      a.cig_arena_cap = static_cast<abm::u32>(std::min<size_t>(ctx->cig_arena.cap, 0xFFFFFF00u));
-    }
-  }
   a.status = d_status;
   a.work = ctx->work.p;
   a.need_big = ctx->need_big.p;
   a.pair_diag = ctx->phase_stamps ? ctx->read_cycles : nullptr;
   a.pair_phases = ctx->phase_stamps ? ctx->pair_phases : nullptr;
-  bool split = ctx->pe_split != 0;  // (0: tier 1 as ONE kernel per pair, as in rounds 1-4 -- same-box comparisons)
-  if (const char *e = experiment_env("ABM_PE_SPLIT")) split = e[0] != '0';
+  ctx->sam_stride = 0;
+  ctx->pe_sam_stride = p.sam_stride;
+  if (text) {  // both ends' records after QNAME, their lengths and a kind per pair, in pinned memory
+    std::memset(ctx->h_pe_kind.p, abm::kPeTextHost, n);  // (a pair no launch finished stays the host's)
+    std::memset(ctx->h_sam_len.p, 0, 2 * n * sizeof(abm::u32));
+    a.blob1 = d_blob1; a.off1 = reinterpret_cast<const abm::u64 *>(d_off1);
+    a.blob2 = d_blob2; a.off2 = reinterpret_cast<const abm::u64 *>(d_off2);
+    a.sam_tail = ctx->h_sam.p;
+    a.sam_len = ctx->h_sam_len.p;
+    a.sam_kind = ctx->h_pe_kind.p;
+    a.sam_stride = p.sam_stride;
+    a.sam_allow_ambig = ctx->sam_allow_ambig;
+    ctx->pe_sam_pairs = n;
+  }
+  const size_t fin_lds = text ? abm::kPeFinBytes : 0;
+  arena_setup(ctx, a, host.host_results, st);
   const size_t events_before = ctx->events_used;
-  const size_t lds1 = abm::pe_lds_bytes(W, WB, a.GW, a.ctmp_cap, eff_len, size_frac, abm::kPeTier1Cap, false) + fin_lds;
+  a.cap = abm::kPeTier1Cap;
   if (!split) {
     // tier 1 unsplit: every pair, seeding and mating in one kernel, small sets in LDS
-    a.cap = abm::kPeTier1Cap;
-    int wps = abm::pe_waves_per_simd(lds1, ctx->phase_stamps, a.G != 0);
-    if (const char *e = experiment_env("ABM_PE_WPS")) { if (!ctx->phase_stamps && a.G != 0 && (e[0] == '3' || e[0] == '4')) wps = e[0] - '0'; }
-    if (text) wps = abm::pe_text_waves_per_simd();  // (the text builds: launch_map_pe)
-    const int waves = abm::pe_resident_waves(lds1, false, wps);
-    if (waves <= 0) throw HipFail("map_pe_kernel (tier 1) does not fit on this device");
-    ctx->payload1.reserve(static_cast<size_t>(waves) * a.cap);
+    const PeLaunch &t1 = p.t1;
+    if (t1.waves <= 0) throw HipFail("map_pe_kernel (tier 1) does not fit on this device");
     a.payload_ws = ctx->payload1.p;
     a.list_ws = nullptr;
-    unsigned long long *counter = ctx->next_read.p + (ctx->launch_seq++ & 63u);
-    HIPCHK(hipMemsetAsync(counter, 0, sizeof(unsigned long long), st));
-    a.next_read = counter;
-    const hipEvent_t e1 = begin_timed(ctx, st);
-    HIPCHK(abm::launch_map_pe(a, lds1, static_cast<abm::u32>(std::min<uint64_t>(n, waves)), false, ctx->phase_stamps, wps, st, text));
-    if (e1) HIPCHK(hipEventRecord(e1, st));
+    a.next_read = fresh_counter(ctx, st);
+    timed_launch(ctx, st, [&] {
+      HIPCHK(abm::launch_map_pe(a, t1.lds, static_cast<abm::u32>(std::min<uint64_t>(n, t1.waves)), false, ctx->phase_stamps, t1.wps, st, text));
+    });
   }
   else {
     // tier 1 split by phase.  SEED: both seed passes of every orientation call's two ends, shaped like the single-end
     // kernel (no alignment state, 6 KB of LDS per wave at 2x150); the finished lists go to the hand-over area.
-    a.cap = abm::kPeTier1Cap;
-    const abm::u32 n_slots = mode == 2 ? 8u : 4u;
-    ctx->hand_hdr.reserve(n * n_slots * 2);
-    ctx->hand_count.reserve(1);
     if (!ctx->split_stats.p) { ctx->split_stats.reserve(4); HIPCHK(hipMemsetAsync(ctx->split_stats.p, 0, 4 * sizeof(unsigned long long), st)); }
-    abm::u32 scap = ctx->pe_scap ? ctx->pe_scap : abm::kPeTier1Cap;  // entries a list may grow to in the seed kernel (beyond kPeTier1Cap: in its staging area)
-    if (const char *e = experiment_env("ABM_PE_SCAP")) scap = static_cast<abm::u32>(std::atoi(e));
-    scap = std::min<abm::u32>(16384, std::max<abm::u32>(abm::kPeTier1Cap, scap));
-    size_t per_pair = scap > abm::kPeTier1Cap ? 256 : 64;  // hand-over entries per pair (a list that finds no room sends its pair to the whole-pair kernel)
-    if (const char *e = experiment_env("ABM_PE_HAND_PER_PAIR")) per_pair = static_cast<size_t>(std::max(4, std::atoi(e)));
-    // (abm_ctx_set_pe_split's hand_entries, when given, is taken as it is: tests run the area out of room with it)
-    const size_t hand_cap = ctx->hand_want ? std::max<size_t>(ctx->hand_want, 64) : std::min<size_t>(std::max<size_t>(n * per_pair, size_t(1) << 16), 0xFFFFFF00u);
-    ctx->hand_pos.reserve(hand_cap);
-    ctx->hand_d.reserve(hand_cap);
     a.hand_hdr = ctx->hand_hdr.p; a.hand_pos = ctx->hand_pos.p; a.hand_d = ctx->hand_d.p;
     a.hand_count = ctx->hand_count.p;
     a.hand_cap = static_cast<abm::u32>(std::min<size_t>(std::min(ctx->hand_pos.cap, ctx->hand_d.cap), 0xFFFFFF00u));
     a.split_stats = ctx->split_stats.p;
     HIPCHK(hipMemsetAsync(ctx->hand_count.p, 0, sizeof(unsigned long long), st));
-    const size_t lds_s = abm::pe_seed_lds_bytes(W, WB, eff_len, a.cap);
-    const int waves_s = abm::pe_seed_resident_waves(lds_s, a.G != 0);
-    if (waves_s <= 0) throw HipFail("map_pe_kernel (seed) does not fit on this device");
-    const abm::u32 grid_s = static_cast<abm::u32>(std::min<uint64_t>(n, waves_s));
-    a.scap = scap;
-    if (scap > a.cap) {
-      ctx->stage_pos.reserve(static_cast<size_t>(grid_s) * scap);
-      ctx->stage_d.reserve(static_cast<size_t>(grid_s) * scap);
-      a.stage_pos = ctx->stage_pos.p; a.stage_d = ctx->stage_d.p;
-    }
+    const PeSeedLaunch &seed = p.seed;
+    if (seed.grid == 0) throw HipFail("map_pe_kernel (seed) does not fit on this device");
+    a.scap = p.scap;
+    if (a.scap > a.cap) { a.stage_pos = ctx->stage_pos.p; a.stage_d = ctx->stage_d.p; }
     a.payload_ws = nullptr;
     a.list_ws = nullptr;
-    {
-      unsigned long long *counter = ctx->next_read.p + (ctx->launch_seq++ & 63u);
-      HIPCHK(hipMemsetAsync(counter, 0, sizeof(unsigned long long), st));
-      a.next_read = counter;
-      const hipEvent_t e1 = begin_timed(ctx, st);
-      HIPCHK(abm::launch_pe_seed(a, lds_s, grid_s, ctx->phase_stamps, st));
-      if (e1) HIPCHK(hipEventRecord(e1, st));
-    }
+    a.next_read = fresh_counter(ctx, st);
+    timed_launch(ctx, st, [&] { HIPCHK(abm::launch_pe_seed(a, seed.lds, seed.grid, ctx->phase_stamps, st)); });
     // MATE, small lists (every list of the pair within kPeTier1Cap entries: LDS): sort, scoring, mating, tracebacks,
     // best_single, fallback -- instruction-bound, it overlaps with the other contexts' seed kernels
-    {
-      const size_t lds_m = abm::pe_mate_lds_bytes(W, a.GW, a.ctmp_cap, eff_len, size_frac, a.cap, false) + fin_lds;
-      const int waves_m = abm::pe_mate_resident_waves(lds_m, false);
-      if (waves_m <= 0) throw HipFail("map_pe_kernel (mate) does not fit on this device");
-      a.order = nullptr;  // (in input order: the lists were handed over in whatever order the seed kernel finished them)
-      unsigned long long *counter = ctx->next_read.p + (ctx->launch_seq++ & 63u);
-      HIPCHK(hipMemsetAsync(counter, 0, sizeof(unsigned long long), st));
-      a.next_read = counter;
-      const hipEvent_t e1 = begin_timed(ctx, st);
+    const size_t lds_m = abm::pe_mate_lds_bytes(s.W, s.GW, s.ctmp_cap, s.eff_len, s.size_frac, a.cap, false) + fin_lds;
+    const int waves_m = abm::pe_mate_resident_waves(lds_m, false);
+    if (waves_m <= 0) throw HipFail("map_pe_kernel (mate) does not fit on this device");
+    a.order = nullptr;  // (in input order: the lists were handed over in whatever order the seed kernel finished them)
+    a.next_read = fresh_counter(ctx, st);
+    timed_launch(ctx, st, [&] {
       HIPCHK(abm::launch_pe_mate(a, lds_m, static_cast<abm::u32>(std::min<uint64_t>(n, waves_m)), false, ctx->phase_stamps, st, text));
-      if (e1) HIPCHK(hipEventRecord(e1, st));
-    }
+    });
   }
   // tier 2: lists and heaps of up to 32768 entries per wave in global memory
   {
     a.cap = abm::kPeCapLarge;
     a.order = nullptr;
-    const size_t lds = abm::pe_lds_bytes(W, WB, a.GW, a.ctmp_cap, eff_len, size_frac, a.cap, true) + fin_lds;
-    int wps = abm::pe_waves_per_simd(lds, ctx->phase_stamps, a.G != 0);
-    if (const char *e = experiment_env("ABM_PE_WPS2")) { if (!ctx->phase_stamps && a.G != 0 && (e[0] == '3' || e[0] == '4')) wps = e[0] - '0'; }
-    if (text) wps = abm::pe_text_waves_per_simd();  // (the text builds: launch_map_pe)
-    int waves = abm::pe_resident_waves(lds, true, wps);
-    if (waves <= 0) throw HipFail("map_pe_kernel (tier 2) does not fit on this device");
-    const size_t lds_mb = abm::pe_mate_lds_bytes(W, a.GW, a.ctmp_cap, eff_len, size_frac, a.cap, true) + fin_lds;
-    int waves_mb = split ? abm::pe_mate_resident_waves(lds_mb, true) : 0;
-    if (split && waves_mb <= 0) throw HipFail("map_pe_kernel (mate, tier 2) does not fit on this device");
-    // (no more waves than the batch has pairs: every wave owns 2.3 MB of lists, heap and log in global memory -- 7.6 GB for
-    // a full grid -- which a batch of a few thousand pairs, or the 32 contexts of two replicas on one device, must not ask for;
-    // abm_ctx_reserve reserves for the batch size it is told)
-    waves = static_cast<int>(std::min<uint64_t>(static_cast<uint64_t>(waves), std::max<uint64_t>(n, 64)));
-    waves_mb = std::min(waves_mb, waves);  // (the two launches share the workspaces)
-    pe_tier2_reserve(ctx, static_cast<size_t>(waves));
+    const PeLaunch &t2 = p.t2;
+    if (t2.waves <= 0) throw HipFail("map_pe_kernel (tier 2) does not fit on this device");
     a.log_ws = ctx->log2.p;
     a.heap_ws = ctx->heap2.p;
     a.payload_ws = ctx->payload2.p;
@@ -914,37 +963,31 @@ void pe_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
     a.work = ctx->work.p + 16;  // tier 2 tallies separately (abm_ctx_take_work_tiers)
     if (split) {
       // the pairs whose lists outgrew LDS inside the seed kernel's staging area: mated from global memory (nothing is seeded twice)
-      ctx->subset_b.reserve(n); ctx->subset_count_b.reserve(1); ctx->class33_b.reserve(33);
+      const size_t lds_mb = abm::pe_mate_lds_bytes(s.W, s.GW, s.ctmp_cap, s.eff_len, s.size_frac, a.cap, true) + fin_lds;
+      const int waves_mb = std::min(abm::pe_mate_resident_waves(lds_mb, true), t2.waves);  // (the two launches share the workspaces)
+      if (waves_mb <= 0) throw HipFail("map_pe_kernel (mate, tier 2) does not fit on this device");
       HIPCHK(abm::launch_collect_big(ctx->need_big.p, ctx->cls.p, n, abm::kRouteBig, ctx->class33_b.p, ctx->subset_b.p, ctx->subset_count_b.p, st));
       a.subset = ctx->subset_b.p; a.subset_count = ctx->subset_count_b.p;
-      unsigned long long *counter = ctx->next_read.p + (ctx->launch_seq++ & 63u);
-      HIPCHK(hipMemsetAsync(counter, 0, sizeof(unsigned long long), st));
-      a.next_read = counter;
-      const hipEvent_t e1 = begin_timed(ctx, st);
-      HIPCHK(abm::launch_pe_mate(a, lds_mb, static_cast<abm::u32>(waves_mb), true, ctx->phase_stamps, st, text));
-      if (e1) HIPCHK(hipEventRecord(e1, st));
+      a.next_read = fresh_counter(ctx, st);
+      timed_launch(ctx, st, [&] { HIPCHK(abm::launch_pe_mate(a, lds_mb, static_cast<abm::u32>(waves_mb), true, ctx->phase_stamps, st, text)); });
       a.subset = ctx->subset.p; a.subset_count = ctx->subset_count.p;
     }
     // the pairs whose candidate sets outgrew tier 1 (the seed kernel): the whole pair again, one wave each, 32768-entry sets
     HIPCHK(abm::launch_collect_big(ctx->need_big.p, ctx->cls.p, n, abm::kRouteWhole, ctx->class33.p, ctx->subset.p, ctx->subset_count.p, st));
-    unsigned long long *counter = ctx->next_read.p + (ctx->launch_seq++ & 63u);
-    HIPCHK(hipMemsetAsync(counter, 0, sizeof(unsigned long long), st));
-    a.next_read = counter;
-    if (ctx->host_results && !has_long) {  // the batch's last launch: its last wave publishes arena count and status to the host
+    a.next_read = fresh_counter(ctx, st);
+    if (host.host_results && !has_long) {  // the batch's last launch: its last wave publishes arena count and status to the host
       HIPCHK(hipMemsetAsync(ctx->finished.p, 0, 4, st));
       a.finished = ctx->finished.p;
       a.host_tail = ctx->h_tail.p;
     }
-    const hipEvent_t e1 = begin_timed(ctx, st);
-    HIPCHK(abm::launch_map_pe(a, lds, static_cast<abm::u32>(waves), true, ctx->phase_stamps, wps, st, text));
-    if (e1) HIPCHK(hipEventRecord(e1, st));
+    timed_launch(ctx, st, [&] { HIPCHK(abm::launch_map_pe(a, t2.lds, static_cast<abm::u32>(t2.waves), true, ctx->phase_stamps, t2.wps, st, text)); });
     a.finished = nullptr;
     a.host_tail = nullptr;
   }
   ctx->pe_timed_launches = static_cast<uint32_t>(ctx->events_used - events_before);
   if (has_long) {
     pe_long_pairs(ctx, a, n, d_blob1, d_off1, d_blob2, d_off2, std::min<abm::u32>(max_len, abm::kMaxReadLen), params->valid_frac, st);
-    if (ctx->host_results) {  // (rare: with a long-end launch the two summary words are copied out after it)
+    if (host.host_results) {  // (rare: with a long-end launch the two summary words are copied out after it)
       HIPCHK(hipMemcpyAsync(&ctx->h_tail.p[0], a.cig_arena_count, 4, hipMemcpyDeviceToHost, st));
       HIPCHK(hipMemcpyAsync(&ctx->h_tail.p[1], a.status, 4, hipMemcpyDeviceToHost, st));
     }
@@ -1023,7 +1066,8 @@ int abm_device_memory(int device, uint64_t *free_bytes, uint64_t *total_bytes) {
 }
 
 // (what pe_device and abm_ctx_reserve allocate on the device for such batches: tier 2's per-wave workspaces, the packed
-// encodings, blobs and offsets, orders and routes, the hand-over area, result slots for the device entry point)
+// encodings, blobs and offsets, orders and routes, the hand-over area, result slots for the device entry point.  The
+// allocations themselves are pe_reserve's and pe_staging_reserve's; this estimate is kept as the CLI's budget knows it)
 int abm_ctx_pe_footprint(abm_ctx *ctx, uint64_t n, uint32_t max_len, uint64_t *bytes) {
   return guarded([&] {
     if (!ctx || !bytes) throw std::invalid_argument("null argument");
@@ -1031,8 +1075,7 @@ int abm_ctx_pe_footprint(abm_ctx *ctx, uint64_t n, uint32_t max_len, uint64_t *b
     HIPCHK(hipSetDevice(ctx->device));
     const uint32_t L = std::min<uint32_t>(std::max<uint32_t>(max_len, 48), abm::kLdsReadLen);
     const uint64_t W = words_for(L);
-    const int waves = pe_tier2_waves(ctx, L, 0.1);
-    const uint64_t w2 = std::min<uint64_t>(static_cast<uint64_t>(std::max(waves, 0)), std::max<uint64_t>(n, 64));
+    const uint64_t w2 = static_cast<uint64_t>(std::max(pe_whole_launch(ctx, launch_shape(ctx, L, 0.1, ShapeKind::kPair), n, true, false).waves, 0));
     const uint64_t cap = abm::kPeCapLarge;
     uint64_t b = w2 * (cap * 4 + 4 * cap * 4 + cap * 4 + (32 + 12 * cap) * 4);  // payload, lists, heap, log
     b += 2 * n * 4 * W * 8;                   // packed encodings of both ends
@@ -1289,10 +1332,8 @@ void abm_ctx_destroy(abm_ctx *c) {
       c->rep->arena = nullptr;
     }
   }
-  c->packed.release(); c->packed2.release(); c->lens2.release(); c->subset.release(); c->subset_count.release(); c->payload1.release(); c->payload2.release(); c->list2.release(); c->heap2.release(); c->log2.release(); c->need_big.release(); c->hand_hdr.release(); c->hand_pos.release(); c->hand_d.release(); c->hand_count.release(); c->split_stats.release(); c->stage_pos.release(); c->stage_d.release(); c->subset_b.release(); c->subset_count_b.release(); c->class33_b.release(); c->pe_out.release(); c->cig2h.release(); c->cig_n2h.release(); c->blob2.release(); c->off2.release(); c->coff.release(); c->scan_tmp.release(); c->cblob.release(); c->lens.release(); c->long_list.release(); c->long_count.release(); c->long_ctmp.release(); c->packed_long.release(); c->packed_long2.release(); c->long_q.release(); c->long_tb.release(); c->order.release(); c->class33.release(); c->cls.release(); c->work.release(); c->next_read.release(); c->cig_arena.release(); c->cig_arena_count.release(); c->h_cn.release(); c->h_slots.release(); c->h_arena.release(); c->h_cn2.release(); c->h_slots2.release(); c->h_rel.release(); c->h_rel2.release(); c->h_res.release(); c->h_pe_out.release(); c->h_sam.release(); c->h_sam_len.release(); c->h_pe_kind.release(); c->h_tail.release(); c->finished.release(); c->blob.release(); c->off.release();
-  c->res.release(); c->cig.release(); c->cig_n.release(); c->status.release();
   for (auto &e : c->events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-  delete c;
+  delete c;  // (the workspaces free themselves, on the device set above)
 }
 
 // work tallies accumulated by every launch since the last read (reset on read):
@@ -1393,7 +1434,7 @@ int abm_map_se_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t
     if (!ctx) throw std::invalid_argument("ctx is null");
     std::lock_guard<std::mutex> lk(ctx->mu);
     se_device(ctx, mode, params, n, d_seq_blob, d_seq_off, max_len, d_res, d_cig, cig_stride, d_cig_n,
-              d_status, static_cast<hipStream_t>(stream));
+              d_status, HostMode{}, static_cast<hipStream_t>(stream));
   });
 }
 
@@ -1417,16 +1458,11 @@ int abm_map_se_batch(abm_ctx *ctx, int mode, const abm_params *params, uint64_t 
     t0.mark("  offsets scanned");
     // one pass: upload, map, hits + compact CIGARs back
     auto run = [&](uint64_t m, const char *blob, uint64_t nbytes, const uint64_t *offs, uint32_t stride, bool take_turn) {
-      ctx->blob.reserve(std::max<uint64_t>(nbytes, 1));
-      ctx->off.reserve(m + 1);
-      ctx->status.reserve(1);
       // The kernel writes hits, op counts and CIGAR slots (28 bytes per read) straight into pinned host memory:
       // device-to-host copies queued behind it are carried out by copy kernels, which get no compute unit while
       // another context's device-filling mapping kernel runs -- a finished batch's results used to sit on the
       // device for as long as the next batch's kernel ran (0.4-0.7 s in the CLI's timeline).
-      ctx->h_res.reserve(m);
-      ctx->h_cn.reserve(m);
-      ctx->h_slots.reserve(m * stride);
+      se_staging_reserve(ctx, m, nbytes);
       HostTrace t2;
       if (nbytes) HIPCHK(hipMemcpyAsync(ctx->blob.p, blob, nbytes, hipMemcpyHostToDevice, st));
       HIPCHK(hipMemcpyAsync(ctx->off.p, offs, (m + 1) * 8, hipMemcpyHostToDevice, st));
@@ -1440,15 +1476,8 @@ int abm_map_se_batch(abm_ctx *ctx, int mode, const abm_params *params, uint64_t 
         std::unique_lock<std::mutex> turn(*ctx->kernel_turn, std::defer_lock);
         if (take_turn) turn.lock();  // (the handful of reads of a long-CIGAR rerun just go ahead)
         __atomic_store_n(ctx->drained, 0u, __ATOMIC_RELAXED);
-        ctx->signal_drained = true;
-        ctx->host_results = true;
-        try {
-          se_device(ctx, mode, params, m, ctx->blob.p, ctx->off.p, max_len, ctx->h_res.p, ctx->h_slots.p, stride, ctx->h_cn.p,
-                    ctx->status.p, st);
-        }
-        catch (...) { ctx->host_results = false; ctx->signal_drained = false; throw; }
-        ctx->host_results = false;
-        ctx->signal_drained = false;
+        se_device(ctx, mode, params, m, ctx->blob.p, ctx->off.p, max_len, ctx->h_res.p, ctx->h_slots.p, stride, ctx->h_cn.p,
+                  ctx->status.p, HostMode{true, true, 0}, st);
         while (__atomic_load_n(ctx->drained, __ATOMIC_RELAXED) == 0u && hipStreamQuery(st) == hipErrorNotReady)
           std::this_thread::sleep_for(std::chrono::microseconds(100));
         if (take_turn) turn.unlock();
@@ -1463,7 +1492,7 @@ int abm_map_se_batch(abm_ctx *ctx, int mode, const abm_params *params, uint64_t 
     };
     // four ops per slot cover nearly every read; longer CIGARs come back through the arena.  If the arena
     // itself ran out (its default size is one op per read), the batch is mapped again with a larger one.
-    const uint32_t stride = 4;
+    const uint32_t stride = kSeHostSlotOps;
     HostTrace tr;
     for (;;) {
       const uint32_t status = run(n, seq_blob + base, bytes, scan.use, stride, true);
@@ -1491,7 +1520,7 @@ int abm_map_se_batch_sliced(abm_ctx *ctx, int mode, const abm_params *params, ui
     std::lock_guard<std::mutex> lk(ctx->mu);
     std::vector<char> delivered(n_slices, 0);
     uint32_t n_delivered = 0;
-    const uint32_t stride = 4;
+    const uint32_t stride = kSeHostSlotOps;
     auto deliver = [&](uint32_t s) {
       delivered[s] = 1;
       ++n_delivered;
@@ -1514,16 +1543,9 @@ int abm_map_se_batch_sliced(abm_ctx *ctx, int mode, const abm_params *params, ui
     // slices complete while the kernel runs unless the batch holds reads of the long-read launch (which follows the
     // ordinary one) or more slices than a 16-bit slice number holds: then they are all handed over at the end
     const bool stream = max_len <= abm::kLdsReadLen && n_slices < 65000u && n < (1ull << 32);
-    ctx->blob.reserve(std::max<uint64_t>(bytes, 1));
-    ctx->off.reserve(n + 1);
-    ctx->status.reserve(1);
-    ctx->h_res.reserve(n);
-    ctx->h_cn.reserve(n);
-    ctx->h_slots.reserve(n * stride);
+    se_staging_reserve(ctx, n, bytes);
     if (stream) {
-      ctx->h_slice_first.reserve(n_slices + 1);
-      ctx->slice_first_d.reserve(n_slices + 1);
-      ctx->h_slice_done.reserve(n_slices);
+      slice_staging_reserve(ctx, n_slices);
       for (uint32_t s = 0; s <= n_slices; ++s) ctx->h_slice_first.p[s] = static_cast<abm::u32>(slice_first[s]);
     }
     HostTrace t2;
@@ -1541,17 +1563,8 @@ int abm_map_se_batch_sliced(abm_ctx *ctx, int mode, const abm_params *params, ui
       {
         std::unique_lock<std::mutex> turn(*ctx->kernel_turn);
         __atomic_store_n(ctx->drained, 0u, __ATOMIC_RELAXED);
-        ctx->signal_drained = true;
-        ctx->host_results = true;
-        ctx->sliced_n = stream ? n_slices : 0;
-        try {
-          se_device(ctx, mode, params, n, ctx->blob.p, ctx->off.p, max_len, ctx->h_res.p, ctx->h_slots.p, stride, ctx->h_cn.p,
-                    ctx->status.p, st);
-        }
-        catch (...) { ctx->host_results = false; ctx->signal_drained = false; ctx->sliced_n = 0; throw; }
-        ctx->host_results = false;
-        ctx->signal_drained = false;
-        ctx->sliced_n = 0;
+        se_device(ctx, mode, params, n, ctx->blob.p, ctx->off.p, max_len, ctx->h_res.p, ctx->h_slots.p, stride, ctx->h_cn.p,
+                  ctx->status.p, HostMode{true, true, stream ? n_slices : 0u}, st);
         // until the kernel is through: pass the turn on once it has handed out its last read, and hand every slice
         // whose completion word has arrived to the caller (slices complete roughly in order: the scan starts at the
         // first one still open)
@@ -1601,22 +1614,10 @@ int abm_ctx_slice_results(abm_ctx *ctx, uint64_t lo, uint64_t hi, abm_hit *out_r
     if (lo > hi || hi > ctx->sliced_reads) throw std::invalid_argument("bad read range");
     const uint64_t m = hi - lo;
     const uint32_t stride = ctx->sliced_stride;
-    const uint32_t *cn = ctx->h_cn.p + lo, *slots = ctx->h_slots.p + lo * stride;
-    out_cig_off[0] = 0;
-    for (uint64_t i = 0; i < m; ++i) out_cig_off[i + 1] = out_cig_off[i] + cn[i];
-    if (out_cig_off[m] > cig_capacity || (out_cig_off[m] && !out_cig_blob)) throw std::length_error("cig_capacity too small");
+    // (the arena's bound here is its capacity: the kernel is still running, its op count not yet published)
+    assemble_cigars(m, stride, ctx->h_cn.p + lo, ctx->h_slots.p + lo * stride, ctx->h_arena.p, ctx->h_arena.cap, out_cig_blob,
+                    cig_capacity, out_cig_off);
     std::memcpy(out_res, ctx->h_res.p + lo, m * sizeof(abm_hit));
-    const uint64_t arena_n = ctx->h_arena.cap;
-    for (uint64_t i = 0; i < m; ++i) {
-      const uint32_t k = cn[i];
-      if (k == 0) continue;
-      const uint32_t *src = slots + i * stride;
-      if (k > stride) {
-        if (static_cast<uint64_t>(src[0]) + k > arena_n) throw std::runtime_error("CIGAR arena reference out of range");
-        src = ctx->h_arena.p + src[0];
-      }
-      std::memcpy(out_cig_blob + out_cig_off[i], src, k * 4ull);
-    }
   });
 }
 
@@ -1709,7 +1710,7 @@ int abm_map_pe_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t
     if (!ctx) throw std::invalid_argument("ctx is null");
     std::lock_guard<std::mutex> lk(ctx->mu);
     pe_device(ctx, mode, params, n, d_seq_blob1, d_seq_off1, d_seq_blob2, d_seq_off2, max_len, d_pair, d_se1,
-              d_se2, d_cig1, d_cig2, cig_stride, d_cig_n1, d_cig_n2, d_status, static_cast<hipStream_t>(stream));
+              d_se2, d_cig1, d_cig2, cig_stride, d_cig_n1, d_cig_n2, d_status, HostMode{}, static_cast<hipStream_t>(stream));
   });
 }
 
@@ -1743,14 +1744,7 @@ int abm_map_pe_batch(abm_ctx *ctx, int mode, const abm_params *params, uint64_t 
     abm_hit *h_se1 = nullptr, *h_se2 = nullptr;
     auto run = [&](uint64_t m, const char *b1, uint64_t nb1, const uint64_t *o1, const char *b2, uint64_t nb2,
                    const uint64_t *o2) {
-      ctx->blob.reserve(std::max<uint64_t>(nb1, 1));
-      ctx->blob2.reserve(std::max<uint64_t>(nb2, 1));
-      ctx->off.reserve(m + 1);
-      ctx->off2.reserve(m + 1);
-      ctx->h_pe_out.reserve(m * 5);  // 20 B pairs + 8 B + 8 B, in units of 8 B
-      ctx->h_cn.reserve(m); ctx->h_cn2.reserve(m);
-      ctx->h_slots.reserve(m * stride); ctx->h_slots2.reserve(m * stride);
-      ctx->status.reserve(1);
+      pe_staging_reserve(ctx, m, nb1, nb2);
       if (nb1) HIPCHK(hipMemcpyAsync(ctx->blob.p, b1, nb1, hipMemcpyHostToDevice, st));
       if (nb2) HIPCHK(hipMemcpyAsync(ctx->blob2.p, b2, nb2, hipMemcpyHostToDevice, st));
       HIPCHK(hipMemcpyAsync(ctx->off.p, o1, (m + 1) * 8, hipMemcpyHostToDevice, st));
@@ -1765,13 +1759,8 @@ int abm_map_pe_batch(abm_ctx *ctx, int mode, const abm_params *params, uint64_t 
       std::memset(ctx->h_cn2.p, 0, m * 4);
       // (no kernel turn here: a paired-end batch ends in a long tail of a few pairs with huge
       // candidate sets, which another context's batch fills)
-      ctx->host_results = true;
-      try {
-        pe_device(ctx, mode, params, m, ctx->blob.p, ctx->off.p, ctx->blob2.p, ctx->off2.p, max_len, h_pair, h_se1,
-                  h_se2, ctx->h_slots.p, ctx->h_slots2.p, stride, ctx->h_cn.p, ctx->h_cn2.p, ctx->status.p, st);
-      }
-      catch (...) { ctx->host_results = false; throw; }
-      ctx->host_results = false;
+      pe_device(ctx, mode, params, m, ctx->blob.p, ctx->off.p, ctx->blob2.p, ctx->off2.p, max_len, h_pair, h_se1,
+                h_se2, ctx->h_slots.p, ctx->h_slots2.p, stride, ctx->h_cn.p, ctx->h_cn2.p, ctx->status.p, HostMode{true, false, 0}, st);
       HIPCHK(hipStreamSynchronize(st));
       const uint32_t status = ctx->h_tail.p[1];
       if (status & ~static_cast<uint32_t>(ABM_STATUS_CIGAR_OVERFLOW | ABM_STATUS_READ_TOO_LONG))
@@ -1807,50 +1796,22 @@ int abm_ctx_reserve(abm_ctx *ctx, uint64_t n, uint32_t max_len, int paired) {
     {
       std::lock_guard<std::mutex> lk(ctx->mu);
       HIPCHK(hipSetDevice(ctx->device));
-      const abm::u32 W = words_for(L);
-      const uint32_t stride = 4;
-      ctx->blob.reserve(n * L); ctx->off.reserve(n + 1);
-      ctx->packed.reserve(n * 4 * W); ctx->lens.reserve(n); ctx->order.reserve(n); ctx->cls.reserve(n); ctx->class33.reserve(33);
-      ctx->status.reserve(1); ctx->cig_arena_count.reserve(1);
-      if (!paired) { ctx->cig.reserve(n * stride); ctx->cig_n.reserve(n); ctx->cig_arena.reserve(std::max<size_t>(1u << 16, 2 * n)); }
-      ctx->h_cn.reserve(n); ctx->h_slots.reserve(n * (paired ? kPeHostSlotOps : stride));
-      // (what se_device asks for: growing any buffer later frees the old one, and hipFree / hipHostFree wait for the whole
-      // device -- i.e. for the other context's mapping kernel -- with the runtime's lock held)
-      ctx->h_arena.reserve(std::max<size_t>({ctx->arena_want, size_t(1) << 16, static_cast<size_t>(paired ? 4 * n : 2 * n)}));
+      // (the launches' own sizing functions, for what the batch entry points ask of them: growing any buffer later frees
+      // the old one, and hipFree / hipHostFree wait for the whole device -- i.e. for the other context's mapping kernel --
+      // with the runtime's lock held)
       if (!paired) {
-        ctx->res.reserve(n); ctx->h_res.reserve(n);
-        if (ctx->sam_on) { ctx->h_sam.reserve(static_cast<size_t>(n) * sam_stride_for(ctx, L, stride)); ctx->h_sam_len.reserve(n); }
+        const LaunchShape s = launch_shape(ctx, L, 0.1, ShapeKind::kSingle);
         // (slices of at least 4096 reads; smaller ones make these buffers grow, which only tests do)
-        const size_t ns = n / 4096 + 2;
-        ctx->slice_id.reserve(n); ctx->slice_left.reserve(ns); ctx->slice_hist.reserve(abm::order_sliced_hist_words(static_cast<abm::u32>(ns)));
-        ctx->slice_first_d.reserve(ns + 1); ctx->h_slice_first.reserve(ns + 1); ctx->h_slice_done.reserve(ns);
+        const uint32_t ns = static_cast<uint32_t>(n / 4096 + 2);
+        se_reserve(ctx, n, s, 0, true, 0);                                                    // abm_map_se_batch's launch
+        se_reserve(ctx, n, s, ns, true, se_text_stride(ctx, s, kSeHostSlotOps, true, true));  // abm_map_se_batch_sliced's
+        se_staging_reserve(ctx, n, n * L);
+        slice_staging_reserve(ctx, ns);
       }
       else {
-        ctx->blob2.reserve(n * L); ctx->off2.reserve(n + 1);
-        ctx->packed2.reserve(n * 4 * W); ctx->lens2.reserve(n);
-        if (ctx->sam_on) {  // (what pe_device asks for with SAM text)
-          ctx->h_sam.reserve(2 * static_cast<size_t>(n) * pe_sam_stride_for(ctx, L, kPeHostSlotOps));
-          ctx->h_sam_len.reserve(2 * n); ctx->h_pe_kind.reserve(n);
-        }
-        ctx->need_big.reserve(n); ctx->subset.reserve(n); ctx->subset_count.reserve(1);
-        // (the phase split's hand-over area and second pair list, sized as pe_device sizes them for a batch of n pairs in the
-        // random-PBAT mode's eight lists per pair: growing them mid-run frees the old ones, and hipFree waits for the whole
-        // device -- the split's first end-to-end run lost half its rate to exactly that, profiles/r05_pe_e2e_regrowth.log)
-        ctx->hand_hdr.reserve(n * 8 * 2); ctx->hand_count.reserve(1);
-        {
-          const abm::u32 scap = std::min<abm::u32>(16384, std::max<abm::u32>(abm::kPeTier1Cap, ctx->pe_scap ? ctx->pe_scap : abm::kPeTier1Cap));
-          const size_t hand_cap = ctx->hand_want ? std::max<size_t>(ctx->hand_want, 64) : std::min<size_t>(std::max<size_t>(n * (scap > abm::kPeTier1Cap ? 256 : 64), size_t(1) << 16), 0xFFFFFF00u);
-          ctx->hand_pos.reserve(hand_cap); ctx->hand_d.reserve(hand_cap);
-        }
-        ctx->subset_b.reserve(n); ctx->subset_count_b.reserve(1); ctx->class33_b.reserve(33);
-        ctx->lens.reserve(n); ctx->order.reserve(n); ctx->cls.reserve(n); ctx->class33.reserve(33); ctx->next_read.reserve(64); ctx->work.reserve(32);
-        ctx->h_pe_out.reserve(n * 5);
-        {  // tier 2's workspaces for batches of n pairs (a full grid of waves from a few thousand pairs on)
-          const int waves = pe_tier2_waves(ctx, L, 0.1);
-          if (waves > 0) pe_tier2_reserve(ctx, static_cast<size_t>(std::min<uint64_t>(static_cast<uint64_t>(waves), std::max<uint64_t>(n, 64))));
-        }
-        ctx->h_slots.reserve(n * kPeHostSlotOps);
-        ctx->h_cn2.reserve(n); ctx->h_slots2.reserve(n * kPeHostSlotOps);
+        const LaunchShape s = launch_shape(ctx, L, 0.1, ShapeKind::kPair);
+        pe_reserve(ctx, n, s, 8, true, pe_plan(ctx, n, s, kPeHostSlotOps, true));  // (the random-PBAT mode's eight lists per pair)
+        pe_staging_reserve(ctx, n, n * L, n * L);
       }
     }
     // a handful of reads through the real entry point: loads the code object, sizes the launch-shape caches

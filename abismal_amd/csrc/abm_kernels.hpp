@@ -213,10 +213,6 @@ hipError_t launch_order_reads_sliced(const DevIndex &ix, const u64 *d_packed, co
                                      u8 *d_cls, const u32 *d_slice_first, u32 n_slices, u16 *d_slice_id, u32 *d_hist,
                                      u32 *d_slice_left, u32 *d_order, hipStream_t st);
 inline size_t order_sliced_hist_words(u32 n_slices) { return static_cast<size_t>(n_slices + 1) * 33 + 33 + n_slices + 2; }
-hipError_t launch_compact_cigars(const Hit *d_res, const u32 *d_cig, const u32 *d_cig_n, u64 n, u32 stride,
-                                 unsigned long long *d_off, u32 *d_blob, void *tmp, size_t *tmp_bytes, hipStream_t st);
-hipError_t launch_gather_cigars(const u32 *d_cig, u32 stride, const unsigned long long *d_off, u64 n, u32 *d_blob,
-                                hipStream_t st);
 // n_waves = one-wave workgroups of the (persistent) grid
 hipError_t launch_map_se(SeArgs a, u32 max_len, u32 n_waves, bool timed, hipStream_t st);
 // the long-read launch (reads of kLdsReadLen + 1 .. kMaxReadLen bases, listed in a.order, packed by list position)
