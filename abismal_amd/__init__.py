@@ -8,7 +8,7 @@ library is missing.
 """
 from .api import (  # noqa: F401
     AbismalAmdError, Index, index_build, Context, Params, lib_path, load_library,
-    SE_T_RICH, SE_A_RICH, SE_RANDOM, PE_NORMAL, PE_PBAT, PE_RANDOM,
+    SE_T_RICH, SE_A_RICH, SE_RANDOM, PE_NORMAL, PE_PBAT, PE_RANDOM, RECORDS_SAM, RECORDS_BAM,
     HIT_DTYPE, PAIR_DTYPE, EXPORTED_SYMBOLS,
 )
 from .build import build  # noqa: F401

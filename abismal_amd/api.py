@@ -8,6 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 SE_T_RICH, SE_A_RICH, SE_RANDOM = 0, 1, 2
 PE_NORMAL, PE_PBAT, PE_RANDOM = 0, 1, 2
+RECORDS_SAM, RECORDS_BAM = 0, 1
 
 HIT_DTYPE = np.dtype([("diffs", "<i2"), ("flags", "<u2"), ("pos", "<u4")])
 PAIR_DTYPE = np.dtype([("aln_score", "<i2"), ("reserved", "<i2"), ("r1", HIT_DTYPE), ("r2", HIT_DTYPE)])
@@ -19,7 +20,7 @@ EXPORTED_SYMBOLS = [
     "abm_map_se_batch", "abm_map_se_batch_sliced", "abm_ctx_slice_results", "abm_map_se_device", "abm_map_pe_batch", "abm_map_pe_device",
     "abm_max_read_length", "abm_ctx_reads_too_long", "abm_ctx_filter_on_planes", "abm_ctx_long_cigars", "abm_ctx_take_work", "abm_ctx_set_phase_stamps", "abm_ctx_set_read_cycles", "abm_ctx_set_timing", "abm_ctx_take_kernel_time", "abm_ctx_take_kernel_times", "abm_ctx_take_work_tiers", "abm_stats_allreduce",
     "abm_device_count", "abm_host_alloc", "abm_host_free", "abm_index_set_seed_extension", "abm_index_set_max_candidates", "abm_index_set_direct_narrowing", "abm_ctx_seed_extension", "abm_ctx_rebuild_seed_extension", "abm_device_numa_node",
-    "abm_ctx_set_pe_split", "abm_ctx_pe_split_stats", "abm_ctx_pe_timed_launches", "abm_ctx_set_pair_phases", "abm_device_memory", "abm_ctx_pe_footprint", "abm_index_set_seed_extension_cap", "abm_ctx_pinned_bytes", "abm_ctx_set_sam_tails", "abm_ctx_slice_sam_tails", "abm_ctx_pe_sam_tails",
+    "abm_ctx_set_pe_split", "abm_ctx_pe_split_stats", "abm_ctx_pe_timed_launches", "abm_ctx_set_pair_phases", "abm_device_memory", "abm_ctx_pe_footprint", "abm_index_set_seed_extension_cap", "abm_ctx_pinned_bytes", "abm_ctx_set_sam_tails", "abm_ctx_slice_sam_tails", "abm_ctx_pe_sam_tails", "abm_ctx_set_record_format",
     "abm_index_set_window_records", "abm_ctx_window_records",
 ]
 
@@ -230,10 +231,13 @@ class Context:
                                           cig_off.ctypes.data))
         return res, cig[: int(cig_off[-1])], cig_off
 
-    def map_se_sliced(self, reads, slice_first, mode=SE_T_RICH, params=None):
+    def map_se_sliced(self, reads, slice_first, mode=SE_T_RICH, params=None, tails=False):
         """abm_map_se_batch_sliced + abm_ctx_slice_results: the batch's results taken slice by slice as the kernel
         completes them.  slice_first: n_slices + 1 read indices (the last one len(reads)).  Returns (hits, cigar_blob,
-        cigar_off) laid out as map_se's for the reads from slice_first[0] on, and the order the slices arrived in."""
+        cigar_off) laid out as map_se's for the reads from slice_first[0] on, and the order the slices arrived in.
+        tails=True (after set_sam_tails) appends a list with one entry per read, taken inside the slice callback with
+        abm_ctx_slice_sam_tails: the record the kernel wrote as bytes, b"" for no record, None for a read left to the
+        host (every read, if the launch wrote none; reads before slice_first[0] too)."""
         params = params or Params()
         blob, off = blob_and_offsets(reads)
         n = len(off) - 1
@@ -242,6 +246,8 @@ class Context:
         res = np.zeros(n, dtype=HIT_DTYPE)
         per_slice, arrived = {}, []
         errors = []
+        records = [None] * n
+        self._lib.abm_ctx_slice_sam_tails.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
 
         def on_done(_user, s):
             try:
@@ -258,6 +264,16 @@ class Context:
                 if s in per_slice:
                     raise AbismalAmdError(f"slice {s} handed over twice")
                 per_slice[s] = (h[:m].copy(), cg[: int(co[m])].copy(), co.copy())
+                if tails and m:
+                    t_p, t_stride, t_lens = C.c_void_p(), C.c_uint32(), C.c_void_p()
+                    _check(self._lib.abm_ctx_slice_sam_tails(self.handle, lo, hi, C.byref(t_p), C.byref(t_stride), C.byref(t_lens)))
+                    if t_p.value:
+                        st = int(t_stride.value)
+                        ln = np.ctypeslib.as_array(C.cast(t_lens.value, C.POINTER(C.c_uint32)), shape=(m,)).copy()
+                        raw = C.string_at(t_p.value, m * st)
+                        for k in range(m):
+                            if int(ln[k]) != 0xFFFFFFFF:
+                                records[lo + k] = raw[k * st:k * st + int(ln[k])]
                 arrived.append(int(s))
             except Exception as e:  # (never let an exception cross the C frame)
                 errors.append(e)
@@ -284,6 +300,8 @@ class Context:
             cig_parts.append(cg)
         cig_off[: int(first[0])] = 0
         cig = np.concatenate(cig_parts) if cig_parts else np.zeros(0, dtype=np.uint32)
+        if tails:
+            return res, cig, cig_off, arrived, records
         return res, cig, cig_off, arrived
 
     def map_se_device(self, mode, params, n, d_blob, d_off, max_len, d_res, d_cig, cig_stride, d_cig_n,
@@ -293,8 +311,15 @@ class Context:
                                            d_res, d_cig, cig_stride, d_cig_n, d_status, stream))
 
     def set_sam_tails(self, on=True, allow_ambig=False):
-        """abm_ctx_set_sam_tails: the kernels write SAM records after QNAME (map_pe(sam=True) returns them)"""
+        """abm_ctx_set_sam_tails: the kernels write SAM records after QNAME -- BAM pieces after set_record_format(bam=True)
+        -- which map_pe(sam=True) and map_se_sliced(tails=True) return"""
         _check(self._lib.abm_ctx_set_sam_tails(self.handle, 1 if on else 0, 1 if allow_ambig else 0))
+
+    def set_record_format(self, bam=False):
+        """abm_ctx_set_record_format: what set_sam_tails makes the kernels write -- SAM text, or with bam=True BAM
+        pieces (abismal_amd.h: the record without its name)"""
+        self._lib.abm_ctx_set_record_format.argtypes = [C.c_void_p, C.c_int]
+        _check(self._lib.abm_ctx_set_record_format(self.handle, RECORDS_BAM if bam else RECORDS_SAM))
 
     def pinned_bytes(self):
         self._lib.abm_ctx_pinned_bytes.argtypes = [C.c_void_p]

@@ -187,6 +187,7 @@ struct abm_ctx {
   // SAM text written by the single-end kernel (abm_ctx_set_sam_tails): the line after QNAME per read, in pinned memory
   bool sam_on = false;
   int sam_allow_ambig = 0;
+  int sam_format = ABM_RECORDS_SAM;  // abm_ctx_set_record_format: what the kernels write into the slots, SAM text or BAM pieces
   uint32_t sam_stride = 0;          // of the launch whose results the buffers hold
   HostBuf<char> h_sam;
   HostBuf<abm::u32> h_sam_len;
@@ -328,6 +329,11 @@ abm::u32 sam_stride_for(const abm_ctx *ctx, abm::u32 eff_len, abm::u32 cig_strid
 }
 // the same for one end of a pair: RNEXT "=", PNEXT and TLEN (up to 10 digits and a sign) in the place of "*\t0\t0"
 abm::u32 pe_sam_stride_for(const abm_ctx *ctx, abm::u32 eff_len, abm::u32 cig_stride) { return sam_stride_for(ctx, eff_len, cig_stride) + 32; }
+// bytes of a slot that holds a BAM piece instead (abm_ctx_set_record_format; BamWriter::piece_len with the widest NM),
+// for a single-end read or one end of a pair alike, in whole 16 bytes
+abm::u32 bam_stride_for(abm::u32 eff_len, abm::u32 cig_stride) {
+  return (36u + 4u * std::min<abm::u32>(cig_stride, abm::kSeCap) + (eff_len + 1) / 2 + eff_len + 9u + 15u) & ~15u;
+}
 abm::u32 bitwords_for(abm::u32 max_len) { return (max_len + 63) / 64 + 1; }
 
 void check_params(const abm_params *p) {
@@ -425,7 +431,8 @@ template <class Args> void arena_setup(abm_ctx *ctx, Args &a, bool pinned, hipSt
 // do not; the host then formats every line as before)
 abm::u32 se_text_stride(const abm_ctx *ctx, const LaunchShape &s, abm::u32 cig_stride, bool host_results, bool sliced) {
   if (!ctx->sam_on || !host_results || !sliced) return 0;
-  const abm::u32 stride = sam_stride_for(ctx, s.eff_len, cig_stride);
+  if (ctx->sam_format == ABM_RECORDS_BAM && ctx->phase_stamps) return 0;  // (the diagnostic builds write no BAM pieces; the pair kernels' write no records at all)
+  const abm::u32 stride = ctx->sam_format == ABM_RECORDS_BAM ? bam_stride_for(s.eff_len, cig_stride) : sam_stride_for(ctx, s.eff_len, cig_stride);
   return stride <= abm::sam_line_room(s.GW, s.tb_extra) ? stride : 0;
 }
 
@@ -569,6 +576,7 @@ void se_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
     a.sam_len = ctx->h_sam_len.p;
     a.sam_stride = sam_stride;
     a.sam_allow_ambig = ctx->sam_allow_ambig;
+    a.sam_format = ctx->sam_format;
   }
   // the occupancy query costs milliseconds: remember it per launch shape
   const uint64_t key = (static_cast<uint64_t>(s.W) << 48) ^ (static_cast<uint64_t>(s.eff_len) << 8) ^ static_cast<uint64_t>(s.size_frac * 255.0);
@@ -741,7 +749,7 @@ PeSeedLaunch pe_seed_launch(const LaunchShape &s, uint64_t n) {
 // only if a line's slot fits the LDS it is built in; otherwise the batch has no text and the host formats it all
 abm::u32 pe_text_stride(const abm_ctx *ctx, const LaunchShape &s, abm::u32 cig_stride, bool host_results) {
   if (!ctx->sam_on || !host_results || ctx->phase_stamps || s.G == 0) return 0;
-  const abm::u32 stride = pe_sam_stride_for(ctx, s.eff_len, cig_stride);
+  const abm::u32 stride = ctx->sam_format == ABM_RECORDS_BAM ? bam_stride_for(s.eff_len, cig_stride) : pe_sam_stride_for(ctx, s.eff_len, cig_stride);
   return stride <= abm::sam_line_room(s.GW, s.tb_extra) ? stride : 0;
 }
 
@@ -905,6 +913,7 @@ void pe_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
     a.sam_kind = ctx->h_pe_kind.p;
     a.sam_stride = p.sam_stride;
     a.sam_allow_ambig = ctx->sam_allow_ambig;
+    a.sam_format = ctx->sam_format;
     ctx->pe_sam_pairs = n;
   }
   const size_t fin_lds = text ? abm::kPeFinBytes : 0;
@@ -1627,6 +1636,15 @@ int abm_ctx_set_sam_tails(abm_ctx *ctx, int enable, int allow_ambig) {
     std::lock_guard<std::mutex> lk(ctx->mu);
     ctx->sam_on = enable != 0;
     ctx->sam_allow_ambig = allow_ambig != 0;
+  });
+}
+
+int abm_ctx_set_record_format(abm_ctx *ctx, int format) {
+  return guarded([&] {
+    if (!ctx) throw std::invalid_argument("ctx is null");
+    if (format != ABM_RECORDS_SAM && format != ABM_RECORDS_BAM) throw std::invalid_argument("record format: ABM_RECORDS_SAM or ABM_RECORDS_BAM");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->sam_format = format;
   });
 }
 

@@ -70,6 +70,11 @@ struct Stats3 { Stats s[3]; };  // SE: s[0]; PE: pairs, read1, read2
 // LDS-list mate kernel 90 -> 152 ms.  Not settled: medians over 8 M pairs, and runs with fewer text contexts per GPU
 // (ABM_CLI_PE_TEXT_CONTEXTS), are still to be taken.
 constexpr unsigned kPeDeviceSamWorkers = 0;
+// BAM output (-B): the same kernels write each record as a BAM piece (abm_ctx_set_record_format) and the formatters put
+// the name in.  The same rule -- fewer host workers per GPU than this -- with thresholds of 0, host records as before,
+// until device pieces are measured end to end at scale (40 M x 100 bp and 2 M pairs 2 x 150 at -t 2 / 4 / 16, three
+// interleaved runs each: DESIGN.md 4.5); ABM_CLI_DEVICE_SAM=1 turns them on.
+constexpr unsigned kSeDeviceBamWorkers = 0, kPeDeviceBamWorkers = 0;
 std::atomic<uint64_t> g_device_records{0}, g_host_records{0};  // SAM / BAM records whose text the kernels / the formatters wrote
 // A batch's FASTQ text: grown with realloc (large blocks are remapped, not copied, and never
 // zero-filled) and recycled through a small pool so that its pages stay faulted in.
@@ -653,6 +658,27 @@ template <class S> void put_bam_record(S &o, const Record &r) {
   const uint32_t bs = static_cast<uint32_t>(end - start - 4);
   size_at[0] = static_cast<unsigned char>(bs); size_at[1] = static_cast<unsigned char>(bs >> 8); size_at[2] = static_cast<unsigned char>(bs >> 16); size_at[3] = static_cast<unsigned char>(bs >> 24);
   o.resize(end);
+}
+// A record the kernels wrote (abismal_amd.h): SAM text after QNAME -- the name goes in front -- or, with -B, a BAM piece:
+// its 36 fixed bytes, block_size and l_read_name taking the name in, then the name and a NUL, then the rest of the piece.
+// Byte for byte what put_record / put_bam_record make of the same read.
+template <class S> inline void put_device_record(S &o, bool bam, const NameRef &name, const char *tail, uint32_t len) {
+  const size_t at0 = o.size();
+  if (!bam) {
+    o.resize(at0 + name.n + len);
+    std::memcpy(&o[at0], name.p, name.n);
+    std::memcpy(&o[at0 + name.n], tail, len);
+    return;
+  }
+  o.resize(at0 + len + name.n + 1);
+  unsigned char *w = reinterpret_cast<unsigned char *>(&o[at0]);
+  std::memcpy(w, tail, 36);
+  const uint32_t bs = (static_cast<uint32_t>(w[0]) | static_cast<uint32_t>(w[1]) << 8 | static_cast<uint32_t>(w[2]) << 16 | static_cast<uint32_t>(w[3]) << 24) + static_cast<uint32_t>(name.n + 1);
+  w[0] = static_cast<unsigned char>(bs); w[1] = static_cast<unsigned char>(bs >> 8); w[2] = static_cast<unsigned char>(bs >> 16); w[3] = static_cast<unsigned char>(bs >> 24);
+  w[12] = static_cast<unsigned char>(name.n + 1);
+  std::memcpy(w + 36, name.p, name.n);
+  w[36 + name.n] = 0;
+  std::memcpy(w + 37 + name.n, tail + 36, len - 36);
 }
 // raw bytes -> BGZF blocks (each an independent gzip member with the BC extra field)
 int g_bgzf_level = 1;  // deflate level of BAM output (-z): 1 = the fast encoder below, 0 = stored, 2..9 = zlib; decoded content is the same at every level
@@ -1383,8 +1409,10 @@ int cmd_map(int argc, char **argv) {
       }
     }
     // single-end SAM text: the kernel writes every read's line after QNAME itself (abm_ctx_set_sam_tails), the formatters
-    // put names in front -- half of the host's CPU time per read was building that text base by base.  BAM records are
-    // built from the fields as before; ABM_CLI_HOST_FORMAT=1: SAM text too (same-box comparisons, tests)
+    // put names in front -- half of the host's CPU time per read was building that text base by base.  With -B the kernel
+    // writes BAM pieces instead and the formatters put the names in (put_device_record); by default, though, BAM records
+    // are still built from the fields on the host: device pieces are unmeasured at scale (kSeDeviceBamWorkers).
+    // ABM_CLI_HOST_FORMAT=1: everything on the host (same-box comparisons, tests)
     // Where it pays: with few host workers per GPU.  40 M reads on one GPU, end to end (profiles/r05_exp_device_sam_text.log):
     // -t 2 12.2-12.4 M reads/s against 8.4 with host formatting, -t 4 13.0-13.5 against 12.9-13.0, -t 16 13.8-13.9 against
     // 14.2-14.3 (the kernel writes 160 bytes more per read across PCIe); process CPU 8.5 s against 12.2 s.  So the device
@@ -1393,12 +1421,12 @@ int cmd_map(int argc, char **argv) {
       const CpuQuota q0;
       unsigned workers = opt.threads ? std::max(1u, opt.threads) : static_cast<unsigned>(std::min<size_t>(std::max<size_t>(topo.n_cores(), 1), 8u + 8u * static_cast<unsigned>(n_gpus)));
       if (q0.cpus > 0 && !std::getenv("ABM_CLI_NO_QUOTA_CLAMP")) workers = std::min(workers, std::max(1u, static_cast<unsigned>(q0.cpus + 0.5)));
-      device_sam = !paired && !opt.bam && !std::getenv("ABM_CLI_NO_STREAM") && !std::getenv("ABM_CLI_HOST_FORMAT") && workers < 12u * static_cast<unsigned>(n_gpus);
+      device_sam = !paired && !std::getenv("ABM_CLI_NO_STREAM") && !std::getenv("ABM_CLI_HOST_FORMAT") && workers < (opt.bam ? kSeDeviceBamWorkers : 12u) * static_cast<unsigned>(n_gpus);
       // paired SAM text: the pair kernels write both ends' records after QNAME (abm_ctx_pe_sam_tails).  Where it pays is
       // taken from measurements on one GPU (kPeDeviceSamWorkers, below); the pinned slots it needs are bounded by
       // pe_text_contexts.
-      if (paired) device_sam = !opt.bam && !std::getenv("ABM_CLI_HOST_FORMAT") && workers < kPeDeviceSamWorkers * static_cast<unsigned>(n_gpus);
-      if (const char *e = std::getenv("ABM_CLI_DEVICE_SAM")) device_sam = !opt.bam && (paired || !std::getenv("ABM_CLI_NO_STREAM")) && e[0] != '0';
+      if (paired) device_sam = !std::getenv("ABM_CLI_HOST_FORMAT") && workers < (opt.bam ? kPeDeviceBamWorkers : kPeDeviceSamWorkers) * static_cast<unsigned>(n_gpus);
+      if (const char *e = std::getenv("ABM_CLI_DEVICE_SAM")) device_sam = (paired || !std::getenv("ABM_CLI_NO_STREAM")) && e[0] != '0';
     }
     if (device_sam && paired) {
       // Pinned memory is what paired text costs: a context's slots hold a whole batch -- two lines of about read length +
@@ -1408,7 +1436,9 @@ int cmd_map(int argc, char **argv) {
       size_t longest_name = 0;
       for (const std::string &nm : ch.names) longest_name = std::max(longest_name, nm.size());
       const size_t batch_pairs = opt.batch ? opt.batch : env_reads("ABM_CLI_BATCH_READS", size_t(1) << 20);
-      const size_t per_ctx = batch_pairs * (2 * (std::max<size_t>(first_len, 48) + longest_name + 192) + 9);
+      // (-B: the BAM slot, abm_api.hip's bam_stride_for with a pair's 8-op slots)
+      const size_t len0 = std::max<size_t>(first_len, 48);
+      const size_t per_ctx = batch_pairs * (2 * (opt.bam ? ((36 + 4 * 8 + (len0 + 1) / 2 + len0 + 9 + 15) & ~size_t(15)) : len0 + longest_name + 192) + 9);
       const long pages = sysconf(_SC_AVPHYS_PAGES), page = sysconf(_SC_PAGESIZE);
       const size_t avail = pages > 0 && page > 0 ? static_cast<size_t>(pages) * static_cast<size_t>(page) : 0;
       const size_t fit = per_ctx ? (avail / 2) / per_ctx : 0;
@@ -1419,8 +1449,9 @@ int cmd_map(int argc, char **argv) {
     }
     if (device_sam)
       for (size_t c = 0; c < ctxs.size(); ++c)
-        if ((!paired || static_cast<int>(c % per_gpu) < pe_text_per_gpu) && abm_ctx_set_sam_tails(ctxs[c], 1, opt.ambig ? 1 : 0) != 0)
-          die_abm("SAM text on the device");
+        if ((!paired || static_cast<int>(c % per_gpu) < pe_text_per_gpu) &&
+            (abm_ctx_set_sam_tails(ctxs[c], 1, opt.ambig ? 1 : 0) != 0 || abm_ctx_set_record_format(ctxs[c], opt.bam ? ABM_RECORDS_BAM : ABM_RECORDS_SAM) != 0))
+          die_abm("records on the device");
     std::vector<std::thread> warm;
     std::exception_ptr werr;
     std::mutex wmu;
@@ -2568,11 +2599,7 @@ int cmd_map(int argc, char **argv) {
           // the kernel wrote the line after QNAME (or found no record: no hit, or one that runs across its chromosome's end)
           if (tl == 0) h.pos = 0;
           else {
-            const NameRef &nm = sl.names[0][k];
-            const size_t at0 = sam.size();
-            sam.resize(at0 + nm.n + tl);
-            std::memcpy(&sam[at0], nm.p, nm.n);
-            std::memcpy(&sam[at0 + nm.n], tail_at, tl);
+            put_device_record(sam, opt.bam, sl.names[0][k], tail_at, tl);
             ++n_device_records;
           }
         }
@@ -2613,11 +2640,7 @@ int cmd_map(int argc, char **argv) {
         for (int e = 0; e < 2; ++e) {
           const uint32_t tl = sl.tail_len[2 * k + e];
           if (tl == 0) continue;
-          const NameRef &nm = sl.names[e][k];
-          const size_t at0 = sam.size();
-          sam.resize(at0 + nm.n + tl);
-          std::memcpy(&sam[at0], nm.p, nm.n);
-          std::memcpy(&sam[at0 + nm.n], tail_at, tl);
+          put_device_record(sam, opt.bam, sl.names[e][k], tail_at, tl);
           tail_at += tl;
           ++n_device_records;
         }

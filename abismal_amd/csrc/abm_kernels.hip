@@ -110,6 +110,8 @@ __global__ __launch_bounds__(256) void make_planes_kernel(const u64 *__restrict_
 // Scalar fields are written byte by byte by lane 0 into an LDS line buffer (a few hundred scalar instructions: 1 % of a
 // read's work), SEQ by all lanes, and the line leaves as 4-byte words, written through like the other results.
 // Returns the line's length, 0 for "no record", 0xFFFFFFFF for "the host formats this one".
+// BAM: the record as a BAM piece instead (BamWriter; SeArgs::sam_format == kRecordsBam picks these builds)
+template <bool BAM>
 __device__ __forceinline__ u32 format_sam_tail(const SeArgs &a, u8 *line /*LDS, 4-byte aligned, a.sam_stride bytes*/, const u32 *fin, u64 r,
                                                u32 L, const Hit &best, u32 n_ops) {
   const bool ambig = (best.flags & kFlagAmbig) != 0;
@@ -120,9 +122,14 @@ __device__ __forceinline__ u32 format_sam_tail(const SeArgs &a, u8 *line /*LDS, 
   u32 chrom = 0, c0 = 0;
   if (!sam_locate(a.ix, best.pos, reflen, chrom, c0)) return 0;
   const bool rc = (best.flags & kFlagRC) != 0;
+  const u32 flag = (rc ? 0x10u : 0u) | ((a.sam_allow_ambig && ambig) ? 0x100u : 0u);
+  if constexpr (BAM) {
+    const BamFields f{static_cast<int>(chrom) - 1, best.pos - c0, reflen, flag, -1, 0u, 0, best.diffs, (best.flags & kFlagARich) != 0};
+    return BamWriter{line, a.sam_stride}.write(f, fin, n_ops, a.blob + a.off[r], L, rc, a.sam_tail + r * a.sam_stride);
+  }
   SamWriter o{line, 0, a.sam_stride};
   o.put('\t');
-  o.put_uint((rc ? 0x10u : 0u) | ((a.sam_allow_ambig && ambig) ? 0x100u : 0u));
+  o.put_uint(flag);
   o.put('\t');
   o.put_chrom(a.ix, chrom);
   o.put('\t');
@@ -137,7 +144,7 @@ __device__ __forceinline__ u32 format_sam_tail(const SeArgs &a, u8 *line /*LDS, 
   return o.w;
 }
 
-template <bool TIMED, bool COOP, bool LONG, bool REC = false>
+template <bool TIMED, bool COOP, bool LONG, bool REC = false, bool BAM = false>
 __device__ __forceinline__ void map_se_body(const SeArgs &a) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int lane = lane_id();
@@ -258,7 +265,7 @@ __device__ __forceinline__ void map_se_body(const SeArgs &a) {
       if (a.sam_tail != nullptr) {
         // (the line buffer: the traceback table's place -- window slots 1.., the window cache and the table's extra bytes --
         // idle once the CIGAR is out; the host asks for at least sam_stride bytes there: sam_line_room)
-        const u32 len = (L > a.max_len) ? 0xFFFFFFFFu : format_sam_tail(a, lds.tb, lds.jpos, r, (L >= a.ix.min_len) ? L : 0u, best, best.pos != 0 ? n_ops : 0u);
+        const u32 len = (L > a.max_len) ? 0xFFFFFFFFu : format_sam_tail<BAM>(a, lds.tb, lds.jpos, r, (L >= a.ix.min_len) ? L : 0u, best, best.pos != 0 ? n_ops : 0u);
         if (lane == 0) store_out(a.sam_len + r, len);
       }
     }
@@ -327,6 +334,10 @@ __device__ __forceinline__ void map_se_body(const SeArgs &a) {
 // REC: the filter reads the window records (DevIndex::wrec) -- a launch none of whose reads is longer than they serve
 template <bool TIMED, bool COOP, bool REC = false>
 __global__ __launch_bounds__(64, ABM_SE_WAVES_PER_SIMD) void map_se_kernel(SeArgs a) { map_se_body<TIMED, COOP, false, REC>(a); }
+// the untimed builds once more, writing BAM pieces where those write SAM text (a launch with SeArgs::sam_format ==
+// kRecordsBam; builds of their own, so that the ones that existed keep their code: DESIGN.md 4.5)
+template <bool COOP, bool REC>
+__global__ __launch_bounds__(64, ABM_SE_WAVES_PER_SIMD) void map_se_bam_kernel(SeArgs a) { map_se_body<false, COOP, false, REC, true>(a); }
 __global__ __launch_bounds__(64, 1) void map_se_long_kernel(SeArgs a) { map_se_body<false, false, true>(a); }
 
 // reads of this batch that the long-read launch takes: kLdsReadLen < length <= kMaxReadLen
@@ -688,17 +699,22 @@ hipError_t launch_map_se(SeArgs a, u32 max_len, u32 n_waves, bool timed, hipStre
   if (a.n_reads == 0) return hipSuccess;
   const size_t lds = se_lds_bytes(a.W, a.WB, a.ctmp_cap, max_len, a.size_frac);
   const u32 blocks = static_cast<u32>(a.n_reads < n_waves ? a.n_reads : n_waves);
+  const bool bam = a.sam_tail != nullptr && a.sam_format == kRecordsBam;
+  if (bam && timed) return hipErrorInvalidValue;  // (no timed build writes BAM pieces: the host leaves such launches without slots)
   // COOP: lanes share a candidate's window on the bit planes (a.G != 0); otherwise one lane per window
   if (a.G != 0 && a.ix.wrec != nullptr && max_len <= a.ix.wrec_max_len && (a.G == 2 || a.G == 4)) {
     if (timed) hipLaunchKernelGGL((map_se_kernel<true, true, true>), dim3(blocks), dim3(64), lds, st, a);
+    else if (bam) hipLaunchKernelGGL((map_se_bam_kernel<true, true>), dim3(blocks), dim3(64), lds, st, a);
     else hipLaunchKernelGGL((map_se_kernel<false, true, true>), dim3(blocks), dim3(64), lds, st, a);
   }
   else if (a.G != 0) {
     if (timed) hipLaunchKernelGGL((map_se_kernel<true, true>), dim3(blocks), dim3(64), lds, st, a);
+    else if (bam) hipLaunchKernelGGL((map_se_bam_kernel<true, false>), dim3(blocks), dim3(64), lds, st, a);
     else hipLaunchKernelGGL((map_se_kernel<false, true>), dim3(blocks), dim3(64), lds, st, a);
   }
   else {
     if (timed) hipLaunchKernelGGL((map_se_kernel<true, false>), dim3(blocks), dim3(64), lds, st, a);
+    else if (bam) hipLaunchKernelGGL((map_se_bam_kernel<false, false>), dim3(blocks), dim3(64), lds, st, a);
     else hipLaunchKernelGGL((map_se_kernel<false, false>), dim3(blocks), dim3(64), lds, st, a);
   }
   return hipGetLastError();

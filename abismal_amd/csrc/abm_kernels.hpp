@@ -54,6 +54,7 @@ struct SeArgs {
   u32 *sam_len;
   u32 sam_stride;
   int sam_allow_ambig;
+  int sam_format;     // kRecordsSam: that text; kRecordsBam: the record as a BAM piece instead (BamWriter, abm_sam.hpp), same slots and lengths
   u32 *read_cycles;   // optional [n], diagnostic kernel only: per-read shader cycles / 1024
   unsigned long long *work;  // optional [16]: seed_iters, search probes, candidates,
                              // read words compared, set updates, alignments
@@ -137,6 +138,7 @@ struct PeArgs {
   u8 *sam_kind;
   u32 sam_stride;
   int sam_allow_ambig;
+  int sam_format;                // as SeArgs::sam_format
 };
 constexpr u8 kRouteSmall = 0, kRouteWhole = 1, kRouteBig = 2;
 // PeArgs::sam_kind: the pair's two records (format_pe), up to two single-end records (format_se: the fallback, or a pair

@@ -747,6 +747,8 @@ template <bool BIG, bool COOP, bool LONG = false, int PHASE = kWhole, bool REC =
 // kPeTextHost -- an end beyond kLdsReadLen bases, a CIGAR beyond `fin`, a line beyond its slot: the host formats the
 // whole pair.  line: the traceback table's place, idle once both CIGARs are out (at least sam_stride bytes: the host
 // checks, sam_line_room); fin: each end's last traceback's first kSeCap ops.
+// BAM: each record as a BAM piece instead (BamWriter; PeArgs::sam_format == kRecordsBam picks these builds)
+template <bool BAM>
 __device__ __forceinline__ void format_pe_tails(const PeArgs &a, u8 *line, const u32 *fin, u64 r, const u32 L[2],
                                                 const PairBest &best, const Hit &h1, const Hit &h2, const u32 n_ops[2]) {
   const int lane = lane_id();
@@ -770,6 +772,15 @@ __device__ __forceinline__ void format_pe_tails(const PeArgs &a, u8 *line, const
         const u32 f1 = 0x1u | 0x2u | 0x40u | (rc1 ? 0x10u : 0u) | (rc2 ? 0x20u : 0u) | amb;
         const u32 f2 = 0x1u | 0x2u | 0x80u | (rc2 ? 0x10u : 0u) | (rc1 ? 0x20u : 0u) | amb;
         for (int e = 0; e < 2; ++e) {
+          if constexpr (BAM) {
+            const BamFields f{static_cast<int>(ch1) - 1, e ? b2 : b1, e ? rl2 : rl1, e ? f2 : f1, static_cast<int>(ch1) - 1, e ? b1 : b2,
+                              e ? -isize : isize, static_cast<i16>(e ? best.d2 : best.d1), ((e ? best.f2 : best.f1) & kFlagARich) != 0};
+            len[e] = BamWriter{line, a.sam_stride}.write(f, fin + e * kSeCap, e ? n_ops[1] : n_ops[0], (e ? a.blob2 + a.off2[r] : a.blob1 + a.off1[r]),
+                                                         e ? L[1] : L[0], e ? rc2 : rc1, a.sam_tail + (2 * r + e) * a.sam_stride);
+            if (len[e] == 0xFFFFFFFFu) { kind = kPeTextHost; break; }
+            wave_sync();  // (the next piece is built where this one was read from)
+            continue;
+          }
           SamWriter o{line, 0, a.sam_stride};
           o.put('\t');
           o.put_uint(e ? f2 : f1);
@@ -802,11 +813,21 @@ __device__ __forceinline__ void format_pe_tails(const PeArgs &a, u8 *line, const
       if (h.pos == 0 || (ambig && !allow)) continue;
       if (nops == 0 || nops > kSeCap) { kind = kPeTextHost; break; }
       u32 chrom = 0, c0 = 0;
-      if (!sam_locate(a.ix, h.pos, sam_ref_len(fin + e * kSeCap, nops), chrom, c0)) continue;
+      const u32 reflen = sam_ref_len(fin + e * kSeCap, nops);
+      if (!sam_locate(a.ix, h.pos, reflen, chrom, c0)) continue;
       const bool rc = (h.flags & kFlagRC) != 0;
+      const u32 flag = (rc ? 0x10u : 0u) | ((allow && ambig) ? 0x100u : 0u);
+      if constexpr (BAM) {
+        const BamFields f{static_cast<int>(chrom) - 1, h.pos - c0, reflen, flag, -1, 0u, 0, h.diffs, (h.flags & kFlagARich) != 0};
+        len[e] = BamWriter{line, a.sam_stride}.write(f, fin + e * kSeCap, nops, (e ? a.blob2 + a.off2[r] : a.blob1 + a.off1[r]), e ? L[1] : L[0], rc,
+                                                     a.sam_tail + (2 * r + e) * a.sam_stride);
+        if (len[e] == 0xFFFFFFFFu) { kind = kPeTextHost; break; }
+        wave_sync();
+        continue;
+      }
       SamWriter o{line, 0, a.sam_stride};
       o.put('\t');
-      o.put_uint((rc ? 0x10u : 0u) | ((allow && ambig) ? 0x100u : 0u));
+      o.put_uint(flag);
       o.put('\t');
       o.put_chrom(a.ix, chrom);
       o.put('\t');
@@ -832,8 +853,10 @@ __device__ __forceinline__ void format_pe_tails(const PeArgs &a, u8 *line, const
 
 // REC: the seed passes filter on the window records (DevIndex::wrec) -- a launch none of whose ends is longer than they serve
 // TEXT: the pair's SAM records are written as well (PeArgs::sam_tail, format_pe_tails)
-template <bool BIG, bool TIMED, bool COOP, int WPS, bool LONG = false, int PHASE = kWhole, bool REC = false, bool TEXT = false>
+// BAM: ... as BAM pieces (TEXT builds of their own, so that the ones that existed keep their code)
+template <bool BIG, bool TIMED, bool COOP, int WPS, bool LONG = false, int PHASE = kWhole, bool REC = false, bool TEXT = false, bool BAM = false>
 __global__ __launch_bounds__(64, WPS) void map_pe_kernel(PeArgs a) {
+  static_assert(!BAM || TEXT, "BAM pieces: a build with the pair's records");
   static_assert(!REC || (COOP && PHASE != kMate), "window records feed the cooperative filter of the seed passes");
   static_assert(!LONG || (BIG && !COOP && !TIMED && PHASE == kWhole), "the long-end launch: tier 2's lists, nibble filter, no stamps");
   static_assert(PHASE != kSeed || !BIG, "the seed kernel keeps its lists in LDS (and its staging area)");
@@ -1075,7 +1098,7 @@ __global__ __launch_bounds__(64, WPS) void map_pe_kernel(PeArgs a) {
       ABM_STAMP(tf1);
       if (TIMED) t_fb += tf1 - tf0;
     }
-    if constexpr (TEXT) format_pe_tails(a, lds.tb, w.fin, r, w.L, best, h1, h2, w.n_ops);
+    if constexpr (TEXT) format_pe_tails<BAM>(a, lds.tb, w.fin, r, w.L, best, h1, h2, w.n_ops);
     if (lane == 0) {
       u32 *po = reinterpret_cast<u32 *>(a.pairs) + r * 5;
       po[0] = static_cast<u32>(static_cast<u16>(static_cast<i16>(best.aln_score)));
@@ -1235,7 +1258,11 @@ hipError_t launch_map_pe(const PeArgs &a, size_t lds, u32 grid, bool big, bool t
     // SAM text: the builds on the bit planes (a.G != 0), four waves per SIMD, the planes for ends the window records would
     // serve as well (the same candidates); lds includes kPeFinBytes
     if (timed || a.G == 0) return hipErrorInvalidValue;
-    if (big) hipLaunchKernelGGL((map_pe_kernel<true, false, true, ABM_PE_WAVES_PER_SIMD, false, kWhole, false, true>), dim3(grid), dim3(64), lds, st, a);
+    if (a.sam_format == kRecordsBam) {
+      if (big) hipLaunchKernelGGL((map_pe_kernel<true, false, true, ABM_PE_WAVES_PER_SIMD, false, kWhole, false, true, true>), dim3(grid), dim3(64), lds, st, a);
+      else hipLaunchKernelGGL((map_pe_kernel<false, false, true, ABM_PE_WAVES_PER_SIMD, false, kWhole, false, true, true>), dim3(grid), dim3(64), lds, st, a);
+    }
+    else if (big) hipLaunchKernelGGL((map_pe_kernel<true, false, true, ABM_PE_WAVES_PER_SIMD, false, kWhole, false, true>), dim3(grid), dim3(64), lds, st, a);
     else hipLaunchKernelGGL((map_pe_kernel<false, false, true, ABM_PE_WAVES_PER_SIMD, false, kWhole, false, true>), dim3(grid), dim3(64), lds, st, a);
     return hipGetLastError();
   }
@@ -1350,7 +1377,11 @@ hipError_t launch_pe_mate(const PeArgs &a, size_t lds, u32 grid, bool big, bool 
   if (grid == 0) return hipSuccess;
   if (text) {  // (SAM text: lds includes kPeFinBytes)
     if (timed) return hipErrorInvalidValue;
-    if (big) hipLaunchKernelGGL((map_pe_kernel<true, false, false, kPeMateWps, false, kMate, false, true>), dim3(grid), dim3(64), lds, st, a);
+    if (a.sam_format == kRecordsBam) {
+      if (big) hipLaunchKernelGGL((map_pe_kernel<true, false, false, kPeMateWps, false, kMate, false, true, true>), dim3(grid), dim3(64), lds, st, a);
+      else hipLaunchKernelGGL((map_pe_kernel<false, false, false, kPeMateWps, false, kMate, false, true, true>), dim3(grid), dim3(64), lds, st, a);
+    }
+    else if (big) hipLaunchKernelGGL((map_pe_kernel<true, false, false, kPeMateWps, false, kMate, false, true>), dim3(grid), dim3(64), lds, st, a);
     else hipLaunchKernelGGL((map_pe_kernel<false, false, false, kPeMateWps, false, kMate, false, true>), dim3(grid), dim3(64), lds, st, a);
     return hipGetLastError();
   }

@@ -1,6 +1,7 @@
 // abismal_amd: SAM text written by the mapping kernels themselves (device side, shared by the single-end kernel's
 // format_sam_tail and the pair kernels' format_pe_tails).  A record's line after QNAME -- put_record of the CLI, byte
-// for byte -- is written by lane 0 into an LDS line buffer, SEQ by all lanes, and leaves as 4-byte words.
+// for byte -- is written by lane 0 into an LDS line buffer, SEQ by all lanes, and leaves as 4-byte words.  BamWriter
+// writes the same record as a BAM piece (put_bam_record of the CLI minus the name) through the same buffer and stores.
 #pragma once
 #include "abm_device.hpp"
 
@@ -92,5 +93,96 @@ __device__ __forceinline__ bool sam_locate(const DevIndex &ix, u32 pos, u32 refl
   const u32 c1 = static_cast<u32>(uni(static_cast<int>(ix.chrom_starts[chrom + 1])));
   return static_cast<u64>(pos) + reflen <= c1;
 }
+
+// ---- the same record as a BAM piece (SeArgs / PeArgs::sam_format == kRecordsBam) ---------------------------------------
+// put_bam_record of the CLI without the read's name, which only the host has.  Bytes [0, 36): block_size (of the record
+// WITHOUT its name) and the 32 fixed bytes, l_read_name 0; bytes [36, len): the CIGAR ops as stored, SEQ two bases a
+// byte (high nibble first), l_seq bytes 0xFF (no qualities), NM with the smallest type that holds it, CV:A.  The host
+// copies the 36 bytes, adds strlen(name) + 1 to block_size and stores it as l_read_name, appends the name and a NUL, then
+// bytes [36, len).
+constexpr int kRecordsSam = 0, kRecordsBam = 1;  // == ABM_RECORDS_*
+
+// reg2bin of the SAM specification (5.3) over [beg, end)
+__device__ __forceinline__ u32 bam_reg2bin(u64 beg, u64 end) {
+  --end;
+  if (beg >> 14 == end >> 14) return static_cast<u32>(((1u << 15) - 1) / 7 + (beg >> 14));
+  if (beg >> 17 == end >> 17) return static_cast<u32>(((1u << 12) - 1) / 7 + (beg >> 17));
+  if (beg >> 20 == end >> 20) return static_cast<u32>(((1u << 9) - 1) / 7 + (beg >> 20));
+  if (beg >> 23 == end >> 23) return static_cast<u32>(((1u << 6) - 1) / 7 + (beg >> 23));
+  if (beg >> 26 == end >> 26) return static_cast<u32>(((1u << 3) - 1) / 7 + (beg >> 26));
+  return 0;
+}
+// 4-bit code of what SEQ shows for read byte c (put_seq's letter, then its index in "=ACMGRSVTWYHKDBN")
+__device__ __forceinline__ u32 bam_seq4(u32 c, bool rc) {
+  if (rc) return c == 'A' ? 8u : c == 'C' ? 4u : c == 'G' ? 2u : c == 'T' ? 1u : 15u;
+  if (c == '=') return 0u;
+  const u32 k = ((c >= 'a' && c <= 'z') ? c - 32u : c) - 'A';
+  // one nibble per letter A .. P and Q .. Z: A 1, B 14, C 2, D 13, G 4, H 11, K 12, M 3, N 15, R 5, S 6, T 8, V 7, W 9, Y 10
+  const u64 tab = k < 16u ? 0xFFF3FCFFB4FFD2E1ull : 0xFFFFFFFAF97F865Full;
+  return k < 26u ? static_cast<u32>(tab >> ((k & 15u) * 4u)) & 15u : 15u;
+}
+struct BamFields {  // what put_bam_record takes from its Record, the name aside
+  int refid;        // the chromosome's number in the BAM header (its place in the index's table less the padding entry)
+  u32 pos, reflen, flag;
+  int next_refid;   // < 0: no mate (next pos is then written as -1 whatever next_pos says)
+  u32 next_pos;
+  int tlen, nm;
+  bool a_rich;
+};
+struct BamWriter {
+  u8 *buf;   // LDS, 4-byte aligned, cap bytes
+  u32 cap;
+  __device__ __forceinline__ static u32 nm_bytes(int nm) { return (nm >= -128 && nm <= 255) ? 4u : 5u; }
+  __device__ __forceinline__ static u32 piece_len(u32 n_ops, u32 L, int nm) { return 36u + 4u * n_ops + (L + 1u) / 2u + L + nm_bytes(nm) + 4u; }
+  // the piece into buf: lane 0 the scalar fields, all lanes the CIGAR, SEQ and the absent qualities (one packed byte
+  // per lane per round).  Returns its length, or 0xFFFFFFFF -- nothing written -- if it is longer than cap.
+  __device__ __forceinline__ u32 put(const BamFields &f, const u32 *fin, u32 n_ops, const char *seq, u32 L, bool rc) const {
+    const u32 len = piece_len(n_ops, L, f.nm);
+    if (len > cap) return 0xFFFFFFFFu;
+    const u32 lane = static_cast<u32>(lane_id());
+    u32 *wd = reinterpret_cast<u32 *>(buf);
+    const u32 packed = (L + 1u) / 2u;
+    u8 *s = buf + 36u + 4u * n_ops;
+    if (lane == 0) {
+      wd[0] = len - 4u;
+      wd[1] = static_cast<u32>(f.refid);
+      wd[2] = f.pos;
+      wd[3] = (255u << 8) | ((bam_reg2bin(f.pos, static_cast<u64>(f.pos) + (f.reflen ? f.reflen : 1u)) & 0xFFFFu) << 16);
+      wd[4] = (n_ops & 0xFFFFu) | ((f.flag & 0xFFFFu) << 16);
+      wd[5] = L;
+      wd[6] = static_cast<u32>(f.next_refid);
+      wd[7] = f.next_refid < 0 ? 0xFFFFFFFFu : f.next_pos;
+      wd[8] = static_cast<u32>(f.tlen);
+      u8 *t = s + packed + L;
+      *t++ = 'N'; *t++ = 'M';
+      if (f.nm >= 0 && f.nm <= 255) { *t++ = 'C'; *t++ = static_cast<u8>(f.nm); }
+      else if (f.nm >= 0) { *t++ = 'S'; *t++ = static_cast<u8>(f.nm); *t++ = static_cast<u8>(f.nm >> 8); }
+      else if (f.nm >= -128) { *t++ = 'c'; *t++ = static_cast<u8>(f.nm); }
+      else { *t++ = 's'; *t++ = static_cast<u8>(f.nm); *t++ = static_cast<u8>(static_cast<u32>(f.nm) >> 8); }
+      *t++ = 'C'; *t++ = 'V'; *t++ = 'A'; *t++ = f.a_rich ? 'A' : 'T';
+    }
+    for (u32 k = lane; k < n_ops; k += 64) wd[9 + k] = fin[k];
+    for (u32 i = lane; i < packed; i += 64) {
+      const u32 j = 2u * i;
+      const u32 hi = bam_seq4(static_cast<u8>(seq[rc ? L - 1u - j : j]), rc);
+      const u32 lo = j + 1u < L ? bam_seq4(static_cast<u8>(seq[rc ? L - 2u - j : j + 1u]), rc) : 0u;
+      s[i] = static_cast<u8>((hi << 4) | lo);
+    }
+    for (u32 i = lane; i < L; i += 64) s[packed + i] = 0xFFu;
+    return len;
+  }
+  // the piece to dst (4-byte aligned) as 4-byte words, written through; all lanes (as SamWriter::flush)
+  __device__ __forceinline__ void flush(u32 *dst, u32 len) const {
+    wave_sync();
+    const u32 *src = reinterpret_cast<const u32 *>(buf);
+    for (u32 k = lane_id(); k < (len + 3) / 4; k += 64) store_out(dst + k, src[k]);
+  }
+  // put, then flush to the record's slot: the piece's length, or 0xFFFFFFFF (the host formats this one)
+  __device__ __forceinline__ u32 write(const BamFields &f, const u32 *fin, u32 n_ops, const char *seq, u32 L, bool rc, char *slot) const {
+    const u32 len = put(f, fin, n_ops, seq, L, rc);
+    if (len != 0xFFFFFFFFu) flush(reinterpret_cast<u32 *>(slot), len);
+    return len;
+  }
+};
 
 }  // namespace abm

@@ -209,6 +209,26 @@ int abm_ctx_slice_sam_tails(abm_ctx *ctx, uint64_t lo, uint64_t hi, const char *
  * line is built in (the single-end launches apply the same guard).  Valid until the context's next mapping call. */
 int abm_ctx_pe_sam_tails(abm_ctx *ctx, uint64_t lo, uint64_t hi, const char **tails, uint32_t *stride,
                          const uint32_t **lens, const uint8_t **kinds);
+/* BAM pieces in the place of SAM text.  With ABM_RECORDS_BAM the same kernels write, into the same slots and under the
+ * same conditions, each record as a BAM piece -- the record `abismal-amd map -B` writes, without the read's name, which
+ * only the host has.  lens and kinds keep their meanings (0: no record; 0xFFFFFFFF / kind 0xFF: the host formats it --
+ * besides the cases above, a CIGAR of more ops than the slot was sized for: 4 single-end, 8 per end of a pair).
+ * A piece of `len` bytes:
+ *   [0, 36)    block_size and the 32 fixed bytes of a BAM alignment record (SAM specification 4.2), little-endian, with
+ *              l_read_name = 0 and block_size counting the record WITHOUT its name: refID and pos (0-based) on the BAM
+ *              header's chromosome list, MAPQ 255, bin = reg2bin(pos, pos + max(reference length, 1)), n_cigar_op,
+ *              FLAG, l_seq, then next refID / next pos / TLEN -- the mate's for a proper pair, else -1, -1, 0;
+ *   [36, len)  the CIGAR ops (length << 4 | op), SEQ two bases a byte (high nibble first, codes of "=ACMGRSVTWYHKDBN",
+ *              the low nibble of the last byte 0 when l_seq is odd; a reverse-strand hit shows the reverse complement),
+ *              l_seq bytes 0xFF (no qualities), "NM" with the smallest of the types C, S, c, s that holds the value, and
+ *              "CV" "A" with the conversion letter.
+ * The host makes a record of a piece in four steps: copy the 36 bytes; add strlen(name) + 1 to block_size and store
+ * (uint8_t)(strlen(name) + 1) as l_read_name (byte 12); append the name and a NUL; append bytes [36, len).
+ * SAM is the default.  The format takes effect with the context's next mapping call (call it before abm_ctx_reserve, which
+ * sizes the slots for the format that is set) and has no effect while abm_ctx_set_sam_tails is off.  A null context or
+ * an unknown value is an error (< 0, text in abm_last_error()). */
+enum { ABM_RECORDS_SAM = 0, ABM_RECORDS_BAM = 1 };
+int abm_ctx_set_record_format(abm_ctx *ctx, int format);
 
 /* Same computation with every buffer already resident in HBM (d_* are device
  * pointers), enqueued on `stream` (a hipStream_t; NULL = default stream) and
