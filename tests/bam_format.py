@@ -1,4 +1,4 @@
-"""Plain-Python restatement of the BAM records of `abismal-amd map -B` (put_bam_record of abm_cli.cpp) in the two parts
+"""Plain-Python restatement of the BAM records of `abismal-amd map -B` (put_bam_record of abm_cli_records.hpp) in the two parts
 the kernels and the host make them from (include/abismal_amd.h): piece() builds a record without its name from the
 fields tests/sam_format.py's record() takes, assemble() puts the name in by the host's four steps."""
 import struct

@@ -1,7 +1,7 @@
 // GPU test program (built and run by tests/test_gpu_bam_records.py): the device's BAM piece writer (BamWriter,
 // abm_sam.hpp) alone, on synthetic fields that mapping on a small genome cannot reach -- every NM type, positions and
 // reference lengths either side of each bin level, every length's packing on both strands, every byte value as a base,
-// 1 to 50 CIGAR ops, a piece beyond its slot -- against a host restatement of put_bam_record (abm_cli.cpp) without
+// 1 to 50 CIGAR ops, a piece beyond its slot -- against a host restatement of put_bam_record (abm_cli_records.hpp) without
 // the name.  One launch, one wave per case.  Prints "OK <n cases>" or the first mismatch.
 #include "../../abismal_amd/csrc/abm_sam.hpp"
 #include <cstdio>

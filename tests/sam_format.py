@@ -1,4 +1,4 @@
-"""Plain-Python restatement of the CLI's paired-end SAM formatting (emit_pe / emit_se / put_record of abm_cli.cpp,
+"""Plain-Python restatement of the CLI's paired-end SAM formatting (emit_pe / emit_se / put_record of abm_cli_records.hpp,
 after select_output and format_pe / format_se of the reference) over map_pe's returned arrays and the index's
 chromosome table: each end's record without QNAME, as the pair kernels write it (abm_ctx_pe_sam_tails)."""
 import bisect
