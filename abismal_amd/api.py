@@ -18,7 +18,7 @@ EXPORTED_SYMBOLS = [
     "abm_index_max_candidates", "abm_index_n_chroms", "abm_index_chrom_name",
     "abm_index_chrom_starts", "abm_index_bytes", "abm_index_build", "abm_index_build_targets", "abm_index_build_opts", "abm_index_window", "abm_ctx_create", "abm_ctx_reserve", "abm_ctx_destroy",
     "abm_map_se_batch", "abm_map_se_batch_sliced", "abm_ctx_slice_results", "abm_map_se_device", "abm_map_pe_batch", "abm_map_pe_device",
-    "abm_max_read_length", "abm_ctx_reads_too_long", "abm_ctx_filter_on_planes", "abm_ctx_long_cigars", "abm_ctx_take_work", "abm_ctx_set_phase_stamps", "abm_ctx_set_read_cycles", "abm_ctx_set_timing", "abm_ctx_take_kernel_time", "abm_ctx_take_kernel_times", "abm_ctx_take_work_tiers", "abm_stats_allreduce",
+    "abm_max_read_length", "abm_ctx_reads_too_long", "abm_ctx_filter_on_planes", "abm_ctx_long_cigars", "abm_ctx_take_work", "abm_ctx_set_phase_stamps", "abm_ctx_set_read_cycles", "abm_ctx_set_timing", "abm_ctx_take_kernel_time", "abm_ctx_take_kernel_times", "abm_ctx_take_work_tiers", "abm_ctx_take_score_iterations", "abm_stats_allreduce",
     "abm_device_count", "abm_host_alloc", "abm_host_free", "abm_index_set_seed_extension", "abm_index_set_max_candidates", "abm_index_set_direct_narrowing", "abm_ctx_seed_extension", "abm_ctx_rebuild_seed_extension", "abm_device_numa_node",
     "abm_ctx_set_pe_split", "abm_ctx_pe_split_stats", "abm_ctx_pe_timed_launches", "abm_ctx_set_pair_phases", "abm_device_memory", "abm_ctx_pe_footprint", "abm_index_set_seed_extension_cap", "abm_ctx_pinned_bytes", "abm_ctx_set_sam_tails", "abm_ctx_slice_sam_tails", "abm_ctx_pe_sam_tails", "abm_ctx_set_record_format",
     "abm_index_set_window_records", "abm_ctx_window_records",
@@ -97,6 +97,8 @@ def load_library():
     lib.abm_ctx_take_kernel_time.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
     lib.abm_ctx_take_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_uint64, C.POINTER(C.c_uint64)]
     lib.abm_ctx_take_work_tiers.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    if hasattr(lib, "abm_ctx_take_score_iterations"):  # (absent from older builds loaded through ABISMAL_AMD_LIB)
+        lib.abm_ctx_take_score_iterations.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     vp = C.c_void_p
     lib.abm_map_se_batch.argtypes = [vp, C.c_int, C.POINTER(Params), C.c_uint64, vp, vp, vp, vp, C.c_uint64, vp]
     lib.abm_map_se_device.argtypes = [vp, C.c_int, C.POINTER(Params), C.c_uint64, vp, vp, C.c_uint32, vp, vp,
@@ -422,6 +424,11 @@ class Context:
         d = dict(zip(keys, [int(x) for x in out[:6]]))
         d["window_cache_hits"] = int(out[11])
         d["single_job_reads"] = int(out[12])  # single-end reads whose set held one alignable entry (scored by the traceback run)
+        if out[10] and hasattr(self._lib, "abm_ctx_take_score_iterations"):
+            # diagnostic kernel only: iterations of the scoring rounds, run / of rounds that run to their last rows
+            it = (C.c_uint64 * 2)()
+            _check(self._lib.abm_ctx_take_score_iterations(self.handle, it))
+            d["score_iterations"], d["score_iterations_full"] = int(it[0]), int(it[1])
         if out[10]:  # diagnostic (stamped) kernel only
             d["light_filter_steps"], d["fifo_updates"], d["filter_steps"] = int(out[13]), int(out[14]), int(out[15])
         if out[10]:

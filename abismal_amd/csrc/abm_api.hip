@@ -440,7 +440,7 @@ abm::u32 se_text_stride(const abm_ctx *ctx, const LaunchShape &s, abm::u32 cig_s
 // this function, so a reserved context grows no buffer mid-run.  n_slices: of a sliced launch, else 0
 void se_reserve(abm_ctx *ctx, uint64_t n, const LaunchShape &s, uint32_t n_slices, bool host_results, abm::u32 sam_stride) {
   ctx->packed.reserve(n * 4 * s.W); ctx->lens.reserve(n);
-  ctx->work.reserve(32); ctx->next_read.reserve(64);
+  ctx->work.reserve(abm::kWorkWords); ctx->next_read.reserve(64);
   if (n < (1ull << 32)) {  // (a larger batch is mapped in input order)
     ctx->order.reserve(n); ctx->cls.reserve(n);
     if (n_slices) { ctx->slice_id.reserve(n); ctx->slice_left.reserve(n_slices); ctx->slice_hist.reserve(abm::order_sliced_hist_words(n_slices)); }
@@ -779,7 +779,7 @@ PePlan pe_plan(const abm_ctx *ctx, uint64_t n, const LaunchShape &s, abm::u32 ci
 // (profiles/r05_pe_e2e_regrowth.log).  mode_slots: lists per pair (8 in the random-PBAT mode, else 4)
 void pe_reserve(abm_ctx *ctx, uint64_t n, const LaunchShape &s, abm::u32 mode_slots, bool host_results, const PePlan &p) {
   ctx->packed.reserve(n * 4 * s.W); ctx->packed2.reserve(n * 4 * s.W); ctx->lens.reserve(n); ctx->lens2.reserve(n);
-  ctx->work.reserve(32); ctx->next_read.reserve(64);
+  ctx->work.reserve(abm::kWorkWords); ctx->next_read.reserve(64);
   ctx->order.reserve(n); ctx->cls.reserve(n); ctx->class33.reserve(33);
   ctx->need_big.reserve(n); ctx->subset.reserve(n); ctx->subset_count.reserve(1);
   if (p.sam_stride) { ctx->h_sam.reserve(static_cast<size_t>(2 * n) * p.sam_stride); ctx->h_sam_len.reserve(2 * n); ctx->h_pe_kind.reserve(n); }
@@ -1318,8 +1318,8 @@ int abm_ctx_create(const abm_index *ix, int device, abm_ctx **out) {
       HIPCHK(hipEventCreateWithFlags(&c->last_done, hipEventDisableTiming));
       HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->drained), sizeof(abm::u32), hipHostMallocMapped | hipHostMallocCoherent));
       *c->drained = 0;
-      c->work.reserve(32);
-      HIPCHK(hipMemset(c->work.p, 0, 32 * sizeof(unsigned long long)));
+      c->work.reserve(abm::kWorkWords);
+      HIPCHK(hipMemset(c->work.p, 0, abm::kWorkWords * sizeof(unsigned long long)));
     }
     catch (...) { abm_ctx_destroy(c); throw; }
     *out = c;
@@ -1390,6 +1390,18 @@ int abm_ctx_take_work_tiers(abm_ctx *ctx, uint64_t out[32]) {
     HIPCHK(hipMemcpy(tmp, ctx->work.p, sizeof(tmp), hipMemcpyDeviceToHost));
     HIPCHK(hipMemset(ctx->work.p, 0, sizeof(tmp)));
     for (int k = 0; k < 32; ++k) out[k] = tmp[k];
+  });
+}
+
+int abm_ctx_take_score_iterations(abm_ctx *ctx, uint64_t out[2]) {
+  return guarded([&] {
+    if (!ctx) throw std::invalid_argument("ctx is null");
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipDeviceSynchronize());
+    unsigned long long tmp[2];
+    HIPCHK(hipMemcpy(tmp, ctx->work.p + abm::kWorkScoreIters, sizeof(tmp), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemset(ctx->work.p + abm::kWorkScoreIters, 0, sizeof(tmp)));
+    out[0] = tmp[0]; out[1] = tmp[1];
   });
 }
 
@@ -1853,7 +1865,7 @@ int abm_ctx_reserve(abm_ctx *ctx, uint64_t n, uint32_t max_len, int paired) {
       std::lock_guard<std::mutex> lk(ctx->mu);
       HIPCHK(hipSetDevice(ctx->device));
       HIPCHK(hipDeviceSynchronize());
-      HIPCHK(hipMemset(ctx->work.p, 0, 32 * sizeof(unsigned long long)));
+      HIPCHK(hipMemset(ctx->work.p, 0, abm::kWorkWords * sizeof(unsigned long long)));
     }
   });
 }

@@ -190,6 +190,7 @@ __device__ __forceinline__ void map_se_body(const SeArgs &a) {
   long long t_begin = 0, t_a = 0, t_b = 0;
   ABM_STAMP(t_begin);
   u32 n_aln = 0, n_single = 0;
+  u32 score_iters[2] = {0, 0};  // (TIMED) iterations of the scoring rounds: run, and of rounds that run to their ends
   bool overflow = false, too_long = false;
 
   // Reads are handed out by one device-wide counter (zeroed before every launch): work per read spans four orders
@@ -256,7 +257,8 @@ __device__ __forceinline__ void map_se_body(const SeArgs &a) {
         }
       }
       ABM_STAMP(t_a);
-      choose_se<LONG>(a.ix, lds, L, a.valid_frac, S, best, cig_out, sink, n_ops, rd_overflow, n_aln, n_single);  // (n_aln, n_single: dead unless TIMED)
+      // (n_aln, n_single, score_iters: dead unless TIMED)
+      choose_se<LONG, !LONG, TIMED>(a.ix, lds, L, a.valid_frac, S, best, cig_out, sink, n_ops, rd_overflow, n_aln, n_single, score_iters);
       overflow |= rd_overflow;
       ABM_STAMP(t_b);
       if (TIMED) wt.t_align += t_b - t_a;
@@ -314,6 +316,8 @@ __device__ __forceinline__ void map_se_body(const SeArgs &a) {
         atomicAdd(&a.work[13], static_cast<unsigned long long>(wt.light_steps));  // filter steps of at most 64 candidates
         atomicAdd(&a.work[14], static_cast<unsigned long long>(wt.fifo_updates));
         atomicAdd(&a.work[15], static_cast<unsigned long long>(wt.steps));
+        atomicAdd(&a.work[kWorkScoreIters], static_cast<unsigned long long>(score_iters[0]));
+        atomicAdd(&a.work[kWorkScoreIters + 1], static_cast<unsigned long long>(score_iters[1]));
       }
     }
   }

@@ -56,9 +56,12 @@ struct SeArgs {
   int sam_allow_ambig;
   int sam_format;     // kRecordsSam: that text; kRecordsBam: the record as a BAM piece instead (BamWriter, abm_sam.hpp), same slots and lengths
   u32 *read_cycles;   // optional [n], diagnostic kernel only: per-read shader cycles / 1024
-  unsigned long long *work;  // optional [16]: seed_iters, search probes, candidates,
+  unsigned long long *work;  // optional [kWorkWords]: seed_iters, search probes, candidates,
                              // read words compared, set updates, alignments
 };
+// the tally buffer: [0, 16) single-end / paired-end tier 1, [16, 32) paired-end tier 2, then two words of the single-end
+// diagnostic build alone: iterations its scoring rounds ran, and iterations of rounds that run to their ends
+constexpr u32 kWorkScoreIters = 32, kWorkWords = 34;
 
 // paired-end launch arguments (abm_kernels_pe.hip)
 struct PeArgs {

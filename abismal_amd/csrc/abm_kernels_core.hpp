@@ -1365,26 +1365,23 @@ struct CigarSink {
   u32 *fin;            // optional: the CIGAR's first kSeCap ops in LDS as well (the single-end kernel's SAM text is made from them)
 };
 
-// build_cigar_len_and_pos + get_traceback (src/AbismalAlign.hpp:166-193, :388-440).
-// Runs uniformly on the wave; ops are collected reversed in LDS then emitted.
-__device__ __forceinline__ void wave_cigar(const u8 *tb, u32 *ctmp, int L, int diffs, int max_diffs,
-                                           int score, int best_r, int best_c, u32 *cig_out,
-                                           const CigarSink &sink, u32 &n_ops, int &ins, int &del, u32 &aln_len,
-                                           u32 &t_pos, bool &overflow) {
+// build_cigar_len_and_pos + get_traceback (src/AbismalAlign.hpp:166-193, :388-440) in two steps, both uniform on the
+// wave: the walk through the traceback table, which leaves the ops reversed in LDS (ctmp) and touches nothing else,
+// and the emission of what the walk found.  Between the two the table may be overwritten (choose_se_pilot does).
+struct CigarWalk {
+  u32 n;                 // ops found (those beyond the scratch's capacity are counted, not kept)
+  int clip_head, clip_tail;
+  int r;                 // the table row the walk ended in
+};
+__device__ __forceinline__ CigarWalk cigar_walk(const u8 *tb, u32 *ctmp, u32 ctmp_cap, int L, int bw, int best_r, int best_c,
+                                                int &ins, int &del) {
   const int lane = lane_id();
   ins = del = 0;  // count_total_ops<I>/<D> with oplen() narrowed to uint8_t (abismal_cigar_utils.hpp:50-53)
-  if (score == 0 || diffs == 0) {
-    if (lane == 0) { store_out(cig_out, static_cast<u32>(L) << 4); if (sink.fin) sink.fin[0] = static_cast<u32>(L) << 4; }
-    n_ops = 1;
-    aln_len = static_cast<u32>(L);
-    return;
-  }
-  const int bw = band_for(diffs, max_diffs);
   int r = best_r, c = best_c;
   const int clip_tail = (L + (bw - 1)) - (r + c);
   u32 n = 0;
   auto emit = [&](u32 run, int op) {
-    if (n < sink.ctmp_cap) { if (lane == 0) ctmp[n] = (run << 4) | static_cast<u32>(op); }
+    if (n < ctmp_cap) { if (lane == 0) ctmp[n] = (run << 4) | static_cast<u32>(op); }
     const int r8 = static_cast<int>(static_cast<u8>(run));
     ins = op == 1 ? static_cast<i16>(ins + r8) : ins;  // (value selects: conditional stores through the two references go to scratch)
     del = op == 2 ? static_cast<i16>(del + r8) : del;
@@ -1410,6 +1407,13 @@ __device__ __forceinline__ void wave_cigar(const u8 *tb, u32 *ctmp, int L, int d
   emit(run, op);
   const int clip_head = (r + c) - (bw - 1);
   wave_sync();
+  return {n, clip_head, clip_tail, r};
+}
+__device__ __forceinline__ void cigar_publish(const u32 *ctmp, const CigarWalk &w, int L, int bw, u32 *cig_out,
+                                              const CigarSink &sink, u32 &n_ops, u32 &aln_len, u32 &t_pos, bool &overflow) {
+  const int lane = lane_id();
+  const u32 n = w.n;
+  const int clip_head = w.clip_head, clip_tail = w.clip_tail;
   // final order: [head clip] reversed(ops) [tail clip]
   const u32 full = n + (clip_head > 0) + (clip_tail > 0);  // the CIGAR's op count
   u32 *dst = cig_out;
@@ -1442,7 +1446,22 @@ __device__ __forceinline__ void wave_cigar(const u8 *tb, u32 *ctmp, int L, int d
   }
   n_ops = full;  // > stride: the ops are in the arena at slot[0] (or, with ABM_STATUS_CIGAR_OVERFLOW set, nowhere complete)
   aln_len = static_cast<u32>(L - clip_tail - clip_head);
-  t_pos = t_pos - static_cast<u32>((bw - 1) / 2) + static_cast<u32>(r);
+  t_pos = t_pos - static_cast<u32>((bw - 1) / 2) + static_cast<u32>(w.r);
+}
+__device__ __forceinline__ void wave_cigar(const u8 *tb, u32 *ctmp, int L, int diffs, int max_diffs,
+                                           int score, int best_r, int best_c, u32 *cig_out,
+                                           const CigarSink &sink, u32 &n_ops, int &ins, int &del, u32 &aln_len,
+                                           u32 &t_pos, bool &overflow) {
+  if (score == 0 || diffs == 0) {
+    ins = del = 0;
+    if (lane_id() == 0) { store_out(cig_out, static_cast<u32>(L) << 4); if (sink.fin) sink.fin[0] = static_cast<u32>(L) << 4; }
+    n_ops = 1;
+    aln_len = static_cast<u32>(L);
+    return;
+  }
+  const int bw = band_for(diffs, max_diffs);
+  const CigarWalk w = cigar_walk(tb, ctmp, sink.ctmp_cap, L, bw, best_r, best_c, ins, del);
+  cigar_publish(ctmp, w, L, bw, cig_out, sink, n_ops, aln_len, t_pos, overflow);
 }
 
 // simple_aln::edit_distance with the reference's integer types
@@ -1662,8 +1681,23 @@ __device__ __forceinline__ int wave_min_i32(int x) {
   for (int d = 32; d >= 1; d >>= 1) x = min(x, __shfl_xor(x, d));
   return x;
 }
+//
+// FLOOR (choose_se_pilot): the caller already holds a score `floor` that some job of the read has reached, and a job
+// that ends below it changes nothing.  Where the match bits are refilled -- every 16 iterations -- each lane bounds
+// what its cells can still lead to: best so far, or the cell's value plus kScoreMatch for each read base the cell has
+// not consumed (a step that consumes a read base gains at most kScoreMatch, a deletion consumes none and gains
+// kScoreIndel <= 0, and a fresh start later in the lane is a start from 0 <= the cell with fewer bases left).  Every
+// later cell of a job descends from the cells its lanes hold now, so once no lane of the wave can still reach `floor`
+// the round ends: each job reports its best so far, which is below `floor`.  A job that would end at `floor` or
+// above always objects, so it runs to its last row and reports its exact score; floor <= 0: no lane is ever below it.
+// `iters`: iterations run (the full run's count is n_total: quad_iterations).
+constexpr int kScoreMatch = 2, kScoreMismatch = -3, kScoreIndel = -4;  // simple_aln's scores (src/AbismalAlign.hpp:51-53)
+static_assert(kScoreMatch > 0 && kScoreMismatch <= kScoreMatch && kScoreIndel <= 0,
+              "the floor's bound: no step gains more than kScoreMatch per read base, and none that consumes no read base gains");
+template <bool FLOOR = false>
 __device__ __forceinline__ void wavefront_quad(const WaveLds &lds, const QuadJob &jp, const QuadJob &jq, int dp, int dq,
-                                               int o, int width, int L, int w_min, int w_max, u32 &bestp, u32 &bestq) {
+                                               int o, int width, int L, int w_min, int w_max, u32 &bestp, u32 &bestq,
+                                               int floor = 0, int *iters = nullptr) {
   const int t_start = max(0, w_min - 1), t_end = 2 * (L - 1 + w_max) + 1;
   const int n_total = (t_end - t_start) / 2 + 1;
   const int W = static_cast<int>(lds.W), GW = static_cast<int>(lds.GW);
@@ -1684,17 +1718,26 @@ __device__ __forceinline__ void wavefront_quad(const WaveLds &lds, const QuadJob
     return every_fourth_bit(lo) | (every_fourth_bit(hi) << 16);
   };
   // +2 on a match, -3 otherwise, in both halves: 5 * bit - 3
+  constexpr unsigned short kStep = kScoreMatch - kScoreMismatch, kMiss = static_cast<unsigned short>(kScoreMismatch);
+  constexpr u32 kGap = static_cast<u32>(static_cast<unsigned short>(kScoreIndel)) * 0x00010001u;
+  static_assert(kStep == 5 && kMiss == 0xFFFD && kGap == 0xFFFCFFFCu, "the packed cell's constants");
   auto step_delta = [&](u32 &M) -> u32 {
     const u16x2 bits = __builtin_bit_cast(u16x2, M & 0x00010001u);
     M >>= 1;
-    const u16x2 five = {5, 5}, minus3 = {0xFFFD, 0xFFFD};
+    const u16x2 five = {kStep, kStep}, minus3 = {kMiss, kMiss};
     return __builtin_bit_cast(u32, static_cast<u16x2>(bits * five + minus3));
+  };
+  // FLOOR: can a cell this lane holds (value cur, last read index q_done) or has held still lead to `floor`?
+  auto alive = [&](const QuadJob &j, u32 cur, u32 best, int q_done) -> bool {
+    const int left = min(max(L - 1 - q_done, 0), L);  // read bases the cell has not consumed
+    const u32 ub = pk_max(best, pk_add(cur, static_cast<u32>(kScoreMatch * left) * 0x00010001u));
+    return ((j.mv & 0xFFFFu) && static_cast<int>(ub & 0xFFFFu) >= floor) || ((j.mv >> 16) && static_cast<int>(ub >> 16) >= floor);
   };
   auto fast = [&](const QuadJob &j, u32 &cur, u32 &M, u32 &best) {
     const u32 lf = static_cast<u32>(from_prev_lane(static_cast<int>(pub))), up = static_cast<u32>(from_next_lane(static_cast<int>(pub)));
     u32 c = pk_max(pk_add(cur, step_delta(M)), 0u);
-    c = pk_max(c, pk_add(up, 0xFFFCFFFCu) & j.ma);  // from_above
-    c = pk_max(c, pk_add(lf, 0xFFFCFFFCu) & j.ml);  // from_left
+    c = pk_max(c, pk_add(up, kGap) & j.ma);  // from_above
+    c = pk_max(c, pk_add(lf, kGap) & j.ml);  // from_left
     cur = c & j.mv;
     best = pk_max(best, cur);
     pub = cur;
@@ -1702,8 +1745,8 @@ __device__ __forceinline__ void wavefront_quad(const WaveLds &lds, const QuadJob
   auto slow = [&](const QuadJob &j, int q, u32 &cur, u32 &M, u32 &best) {
     const u32 lf = static_cast<u32>(from_prev_lane(static_cast<int>(pub))), up = static_cast<u32>(from_next_lane(static_cast<int>(pub)));
     u32 c = pk_max(pk_add(cur, step_delta(M)), 0u);
-    c = pk_max(c, pk_add(up, 0xFFFCFFFCu) & (q < L - 1 ? j.ma : 0u));  // from_above
-    c = pk_max(c, pk_add(lf, 0xFFFCFFFCu) & (q > 0 ? j.ml : 0u));      // from_left
+    c = pk_max(c, pk_add(up, kGap) & (q < L - 1 ? j.ma : 0u));  // from_above
+    c = pk_max(c, pk_add(lf, kGap) & (q > 0 ? j.ml : 0u));      // from_left
     cur = static_cast<u32>(q) < static_cast<u32>(L) ? (c & j.mv) : 0u;
     best = pk_max(best, cur);
     pub = cur;
@@ -1713,7 +1756,12 @@ __device__ __forceinline__ void wavefront_quad(const WaveLds &lds, const QuadJob
   for (int seg = 0; seg < 3; ++seg) {
     const int end = seg == 0 ? n_mid0 : (seg == 1 ? n_mid1 : n_total);
     while (n < end) {
-      if ((n & 15) == 0) { Mp = refill(jp, n + q0p); Mq = refill(jq, n + q0q); }
+      if ((n & 15) == 0) {
+        if constexpr (FLOOR) {
+          if (n != 0 && !__any(alive(jp, curp, bestp, n - 1 + q0p) || alive(jq, curq, bestq, n - 1 + q0q))) { *iters = n; return; }
+        }
+        Mp = refill(jp, n + q0p); Mq = refill(jq, n + q0q);
+      }
       const int stop = min(end, (n | 15) + 1);
       if (seg == 1) {
         for (; n < stop; ++n) { fast(jp, curp, Mp, bestp); fast(jq, curq, Mq, bestq); }
@@ -1723,11 +1771,18 @@ __device__ __forceinline__ void wavefront_quad(const WaveLds &lds, const QuadJob
       }
     }
   }
+  if constexpr (FLOOR) *iters = n_total;
+}
+// iterations of a round that runs to its end (bands of w_min .. w_max lanes)
+__device__ __forceinline__ int quad_iterations(int L, int w_min, int w_max) {
+  return (2 * (L - 1 + w_max) + 1 - max(0, w_min - 1)) / 2 + 1;
 }
 
 // score_round with four jobs per slot: job first+4m+h of slot m is set (h & 1), half (h >> 1)
+// FLOOR: see wavefront_quad; iters[0] += iterations run, iters[1] += iterations of the full run
+template <bool FLOOR = false>
 __device__ __forceinline__ int score_round_quad(const DevIndex &ix, const WaveLds &lds, int first, int n_jobs, int L, int md,
-                                                int qbase) {
+                                                int qbase, int floor = 0, u32 *iters = nullptr) {
   const int lane = lane_id();
   QuadJob ja = {0, 0, 0, 0, 0, 0, 0, 0, 0}, jb = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   int used = 0, s = first, w_min = 64, w_max = 0, my_o = 0, my_w = 0;
@@ -1772,7 +1827,13 @@ __device__ __forceinline__ int score_round_quad(const DevIndex &ix, const WaveLd
   const int t_start = max(0, w_min - 1);
   const bool even = ((t_start - my_o) & 1) == 0;  // which of the lane's sets is due on even steps
   u32 bp, bq;
-  wavefront_quad(lds, even ? ja : jb, even ? jb : ja, even ? 0 : 1, even ? 1 : 0, my_o, my_w, L, w_min, w_max, bp, bq);
+  if constexpr (FLOOR) {
+    int ran = 0;
+    wavefront_quad<true>(lds, even ? ja : jb, even ? jb : ja, even ? 0 : 1, even ? 1 : 0, my_o, my_w, L, w_min, w_max, bp, bq, floor, &ran);
+    iters[0] += static_cast<u32>(ran);
+    iters[1] += static_cast<u32>(quad_iterations(L, w_min, w_max));
+  }
+  else wavefront_quad(lds, even ? ja : jb, even ? jb : ja, even ? 0 : 1, even ? 1 : 0, my_o, my_w, L, w_min, w_max, bp, bq);
   const u32 best_a = even ? bp : bq, best_b = even ? bq : bp;
   int base = 0, mine = 0;
   for (int k = first; k < s;) {
@@ -1813,11 +1874,71 @@ __device__ __forceinline__ int score_jobs(const DevIndex &ix, const WaveLds &lds
   return score_round<WRAP>(ix, lds, first, n_jobs, L, md, qbase);
 }
 
+// (list_se_jobs and first_maximum restate what choose_se does inline, for choose_se_pilot: called from choose_se they
+// changed the register allocation of two pair kernels, and those are to stay what they were.  Two copies to keep in
+// step: a change to either helper must be mirrored in choose_se's body, and the other way round.)
+// prepare_for_alignments (src/abismal.cpp:1435-1497): the set's entries ordered by (pos, flags), duplicates dropped,
+// as the job list in LDS (jpos / jdf).  Returns the number of jobs.  Lane k looks
+// at heap entry k; its payload sits in lane (key & 255).
+__device__ __forceinline__ int list_se_jobs(const WaveLds &lds, const SeSet &S, int Ls) {
+  const int lane = lane_id();
+  const bool mine = lane < S.sz;
+  const int slot_of = S.hk & 255;
+  const u32 e_pos = __shfl(S.pp, slot_of), e_flags = __shfl(S.pf, slot_of);
+  const int e_d = SeSet::key_d(S.hk);
+  const u64 key = (static_cast<u64>(e_pos) << 16) | e_flags;
+  bool dup = false;
+  for (int k = 0; k < S.sz; ++k) {
+    const u64 kk = rdlane(key, k);
+    dup |= (mine && k < lane && kk == key);
+  }
+  // jobs = unique entries that the reference would align: non-empty, diffs < 0.4L
+  const int invalid_at = static_cast<i16>(0.4 * Ls);  // valid_hit, :323-326
+  const bool is_job = mine && !dup && e_pos != 0 && e_d < invalid_at;
+  const u64 jobs = __ballot(is_job);
+  int rank = 0;
+  for (int k = 0; k < S.sz; ++k) {
+    const u64 kk = rdlane(key, k);
+    rank += ((jobs >> k) & 1) && kk < key;
+  }
+  const int n_jobs = __popcll(jobs);
+  if (is_job) {
+    lds.jpos[rank] = e_pos;
+    lds.jdf[rank] = (static_cast<u32>(e_d) << 16) | e_flags;
+  }
+  wave_sync();
+  return n_jobs;
+}
+
+// the first maximum of a traceback run's table in row-major order (max value, then smallest row, then smallest
+// column) from each lane's best cell of its own column: score, row, column
+__device__ __forceinline__ void first_maximum(int bw, int bv, int brow, int &sc, int &br, int &bc) {
+  const int lane = lane_id();
+  const u64 k64 = (static_cast<u64>(static_cast<u32>(bv)) << 32) |
+                  (static_cast<u64>(0xFFFFu - static_cast<u32>(brow)) << 8) |
+                  static_cast<u64>(0xFFu - static_cast<u32>(lane));
+  const u64 topk = wave_max_u64(lane < bw ? k64 : 0ull);
+  br = static_cast<int>(0xFFFFu - static_cast<u32>((topk >> 8) & 0xFFFFu));
+  bc = static_cast<int>(0xFFu - static_cast<u32>(topk & 0xFFu));
+  sc = static_cast<i16>(static_cast<int>(topk >> 32));
+}
+
+template <bool TALLY>
+__device__ __forceinline__ void choose_se_pilot(const DevIndex &ix, const WaveLds &lds, u32 L, double frac, SeSet &S, Hit &best,
+                                                u32 *cig_out, const CigarSink &sink, u32 &n_ops, bool &overflow, u32 &n_aln,
+                                                u32 &n_single, u32 *iters);
+
 // align_se_candidates (src/abismal.cpp:1435-1497) on the wave-resident set
-template <bool WRAP = false>
+// PILOT (the single-end kernels for reads that fit LDS): choose_se_pilot's order of the same work; iters: its tallies
+template <bool WRAP = false, bool PILOT = false, bool TALLY = false>
 __device__ __forceinline__ void choose_se(const DevIndex &ix, const WaveLds &lds, u32 L, double frac,
                                           SeSet &S, Hit &best, u32 *cig_out, const CigarSink &sink,
-                                          u32 &n_ops, bool &overflow, u32 &n_aln, u32 &n_single) {
+                                          u32 &n_ops, bool &overflow, u32 &n_aln, u32 &n_single, u32 *iters = nullptr) {
+  if constexpr (PILOT) {
+    static_assert(!WRAP && kTracebackByRows && kQuadMinJobs <= 1, "the pilot order: 32-bit scores, every round on the packed cells");
+    choose_se_pilot<TALLY>(ix, lds, L, frac, S, best, cig_out, sink, n_ops, overflow, n_aln, n_single, iters);
+    return;
+  }
   const int lane = lane_id();
   const int Ls = static_cast<i16>(L);
   const int md = static_cast<i16>(frac * static_cast<u32>(Ls));  // valid_diffs_cutoff
@@ -1936,5 +2057,125 @@ __device__ __forceinline__ void choose_se(const DevIndex &ix, const WaveLds &lds
   // like the reference's r.cig, so that count and slot -- or arena reference -- always belong together)
 }
 
+
+// choose_se for the kernels whose reads fit LDS, with the work in another order and the same outcome.  The outcome is
+// a function of the maximum score M over the jobs, the first job (in list order) that reaches M, and the later jobs
+// that equal M; what a job below M scores exactly is never seen.  So, with two jobs or more:
+//   1. the job with the fewest mismatches (the lowest index among equals) is the pilot: its traceback run comes first
+//      -- the same table as its scoring run, so the table's maximum is the pilot's score Sp (as for a lone job);
+//   2. the pilot's CIGAR is walked out of the table into ctmp and held back: the scoring rounds overwrite the table
+//      (it overlays the window slots), and nothing is published before the pilot is confirmed;
+//   3. the other jobs are scored in rounds against a floor (wavefront_quad<true>): Sp, then the best score seen.  A
+//      round ends once none of its jobs can reach the floor; those jobs report less than the floor, hence less than M;
+//   4. the reference's selection runs in list order over all scores, Sp in the pilot's place.  A job below M may take
+//      the lead early or tie with a leader below M -- the first job at M overwrites both, as in the reference;
+//   5. the pilot won: its held CIGAR is published.  Another job won (a tie from a lower position, or a gapped
+//      alignment that beats the pilot): its traceback runs as in choose_se, over the held ops.
+// The traceback code exists once: the loop below passes through it for the pilot and, if need be, again for the winner.
+template <bool TALLY>
+__device__ __forceinline__ void choose_se_pilot(const DevIndex &ix, const WaveLds &lds, u32 L, double frac, SeSet &S, Hit &best,
+                                                u32 *cig_out, const CigarSink &sink, u32 &n_ops, bool &overflow, u32 &n_aln,
+                                                u32 &n_single, u32 *iters) {
+  const int lane = lane_id();
+  const int Ls = static_cast<i16>(L);
+  const int md = static_cast<i16>(frac * static_cast<u32>(Ls));  // valid_diffs_cutoff
+  const int perfect = static_cast<i16>(2 * L);
+  n_ops = 0;
+  if (S.best_p != 0) {  // exact match: no alignment needed
+    best.diffs = static_cast<i16>(S.best_d); best.flags = static_cast<u16>(S.best_f); best.pos = S.best_p;
+    if (lane == 0) { store_out(cig_out, L << 4); if (sink.fin) sink.fin[0] = L << 4; }
+    n_ops = 1;
+    return;
+  }
+  const int n_jobs = list_se_jobs(lds, S, Ls);
+  best.diffs = 0x7fff; best.flags = 0; best.pos = 0;
+  if (n_jobs == 0) return;
+  const bool single = n_jobs == 1;
+  int pilot = 0;
+  if (!single) pilot = wave_min_i32(lane < n_jobs ? static_cast<int>(((lds.jdf[lane] >> 16) << 8) | static_cast<u32>(lane)) : 0x7fffffff) & 255;
+  const u32 p_pos = lds.jpos[pilot], p_df = lds.jdf[pilot];
+  int trace = pilot;  // the list entry under traceback
+  int top = 0, b_diffs = static_cast<int>(p_df) >> 16;
+  u32 b_pos = p_pos, b_flags = p_df & 0xFFFFu;
+  for (bool pilot_pass = !single;; pilot_pass = false) {
+    // traceback run of list entry `trace`: one job, band in lanes [0, bw), its window in slot 0
+    const int bw = band_for(b_diffs, md);
+    AlnJob job = {0, 0, 0, 0, 0};
+    const u64 t_beg = static_cast<u64>(b_pos) - static_cast<u64>((bw - 1) / 2);
+    if (lane < bw) {
+      job.bw = bw;
+      job.jl = lane;
+      job.qoff = static_cast<int>(enc_of(b_flags) * lds.W);
+      job.t0nib = static_cast<int>(t_beg & 15u);
+    }
+    stage_windows(ix, lds, trace, 1, md);
+    wave_sync();
+    int bv, brow, sc, br, bc;
+    wavefront_rows<true>(lds, job, static_cast<int>(L), bw, bv, brow);
+    first_maximum(bw, bv, brow, sc, br, bc);
+    wave_sync();
+    // (wave_cigar's shortcut for a job without mismatches or without a score is not needed: a set entry has d >= 1 --
+    // SeSet::admit keeps d == 0 apart as the exact match, which returned above -- and only a score > 0 is published)
+    CigarWalk walk = {0, 0, 0, 0};
+    int n_ins = 0, n_del = 0;
+    if (sc > 0) walk = cigar_walk(lds.tb, lds.ctmp, sink.ctmp_cap, static_cast<int>(L), bw, br, bc, n_ins, n_del);
+    if (single) {  // what the scoring run would have found
+      ++n_aln;
+      ++n_single;
+      top = sc;
+      if (sc <= 0) { best.flags = static_cast<u16>(kFlagAmbig); return; }  // (a zero score ties with "nothing yet" at position 0)
+      best.flags = static_cast<u16>(b_flags);
+    }
+    if (pilot_pass) {
+      // the pilot leaves the list (the entries behind it move up), the rest is scored against the floor
+      u32 mv_pos = 0, mv_df = 0;
+      const bool moves = lane > pilot && lane < n_jobs;
+      if (moves) { mv_pos = lds.jpos[lane]; mv_df = lds.jdf[lane]; }
+      wave_sync();
+      if (moves) { lds.jpos[lane - 1] = mv_pos; lds.jdf[lane - 1] = mv_df; }
+      wave_sync();
+      const int n_rest = n_jobs - 1;
+      int floor = sc, b_at = -1;  // b_at: the leader's list entry, -1 = the pilot
+      u32 top_pos = 0;
+      top = 0; b_pos = 0; b_flags = 0; b_diffs = 0x7fff;
+      auto select = [&](int at, u32 pos, u32 df, int s) {  // the reference's selection, in job order
+        const u32 flags = df & 0xFFFFu;
+        ++n_aln;
+        if (s > top) { b_diffs = static_cast<int>(df) >> 16; b_flags = flags; b_pos = pos; top = s; top_pos = pos; b_at = at; }
+        else if (s == top) {
+          const u32 gap = pos > top_pos ? pos - top_pos : top_pos - pos;
+          if (s == perfect ? pos != top_pos : gap > 3u) b_flags |= kFlagAmbig;
+        }
+      };
+      u32 it[2] = {0, 0};
+      for (int s = 0; s < n_rest;) {
+        const int first = s;
+        s = score_round_quad<true>(ix, lds, first, n_rest, static_cast<int>(L), md, 0, floor, it);
+        for (int k = first; k < s; ++k) {
+          if (k == pilot) select(-1, p_pos, p_df, sc);
+          const int sk = static_cast<i16>(lds.lbest[k - first]);
+          select(k, lds.jpos[k], lds.jdf[k], sk);
+          floor = max(floor, sk);
+        }
+        wave_sync();
+      }
+      if (pilot == n_rest) select(-1, p_pos, p_df, sc);
+      if (TALLY) { iters[0] += it[0]; iters[1] += it[1]; }
+      best.flags = static_cast<u16>(b_flags);
+      if (b_pos == 0) return;
+      if (b_at >= 0) { trace = b_at; continue; }  // not the pilot: the held ops are dropped
+    }
+    u32 alen = 0, pos = b_pos;
+    cigar_publish(lds.ctmp, walk, static_cast<int>(L), bw, cig_out, sink, n_ops, alen, pos, overflow);
+    wave_sync();
+    // NM from the score found by the scoring pass (best_scr), as the reference does
+    const int nm = edit_distance(top, alen, n_ins, n_del);
+    if (long_enough(alen, static_cast<u32>(Ls), ix.min_len) && nm <= md) {
+      best.diffs = static_cast<i16>(nm);
+      best.pos = pos;
+    }
+    return;
+  }
+}
 
 }  // namespace abm

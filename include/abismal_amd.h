@@ -332,6 +332,10 @@ int abm_ctx_set_phase_stamps(abm_ctx *ctx, int enable);
  * fallback, [10] total, [12] sort+unique, [13] pairable-entry alignments,
  * [14] mating + tracebacks, [15] best_single replay. */
 int abm_ctx_take_work_tiers(abm_ctx *ctx, uint64_t out[32]);
+/* Diagnostic build of the single-end kernel only: [0] iterations its scoring rounds ran since the previous call,
+ * [1] iterations the same rounds take when each runs to its last row (a round ends early once none of its jobs can
+ * still reach a score another job of the read has reached: DESIGN.md 4.1).  Reset by the call. */
+int abm_ctx_take_score_iterations(abm_ctx *ctx, uint64_t out[2]);
 /* Diagnostic kernel only: device array [n] receiving per-read shader cycles / 1024 (NULL = off). */
 int abm_ctx_set_read_cycles(abm_ctx *ctx, uint32_t *d_read_cycles);
 /* Paired-end diagnostic kernels only: device array [n][8] (zeroed by the caller) to which the kernels that mate a pair add
