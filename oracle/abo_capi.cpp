@@ -18,6 +18,7 @@ template <class F> int guarded(F &&f) {
   try { f(); return 0; }
   catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
+constexpr int kWorkValues = 11;
 struct MapperBox {
   const Index *ix;
   MapParams par;
@@ -98,11 +99,12 @@ void abo_mapper_free(void *p) { delete static_cast<MapperBox *>(p); }
 // Reads are trimmed ASCII, concatenated in `blob` with n+1 offsets.  Results:
 // out[i] as the reference's bests[i] just before format_se, CIGARs as BAM u32
 // ops in fixed slots of `cig_stride` per read with their count in cig_n[i].
-// work9 (optional) accumulates the Work tallies.  threads>1 splits the batch
+// work (optional, kWorkValues = 11 values) accumulates the Work tallies: the nine of the
+// algorithmic-bytes model, then the blank-nibble probes of the 2-letter and 3-letter tables.  threads>1 splits the batch
 // into contiguous shards, one Mapper per thread.
 int abo_map_se(void *mapper, int mode, uint64_t n, const char *blob, const uint64_t *off,
                abo_hit *out, uint32_t *cig, uint32_t cig_stride, uint32_t *cig_n,
-               unsigned threads, uint64_t *work9) {
+               unsigned threads, uint64_t *work) {
   MapperBox *b = static_cast<MapperBox *>(mapper);
   std::atomic<int> bad{0};
   std::vector<Work> works(std::max(1u, threads));
@@ -133,11 +135,11 @@ int abo_map_se(void *mapper, int mode, uint64_t n, const char *blob, const uint6
   for (unsigned t = 0; t < nt; ++t)
     th.emplace_back(shard, t, n * t / nt, n * (t + 1) / nt);
   for (auto &x : th) x.join();
-  if (work9) {
+  if (work) {
     for (const Work &w : works) {
-      const uint64_t v[9] = {w.reads, w.seed_iters, w.search_probes, w.candidates, w.words,
-                             w.set_updates, w.aligns, w.aligns_tb, w.dp_cells};
-      for (int k = 0; k < 9; ++k) work9[k] += v[k];
+      const uint64_t v[kWorkValues] = {w.reads, w.seed_iters, w.search_probes, w.candidates, w.words, w.set_updates,
+                                       w.aligns, w.aligns_tb, w.dp_cells, w.blank_probes2, w.blank_probes3};
+      for (int k = 0; k < kWorkValues; ++k) work[k] += v[k];
     }
   }
   if (bad) { g_err = "oracle shard failed"; return -1; }
@@ -147,7 +149,7 @@ int abo_map_se(void *mapper, int mode, uint64_t n, const char *blob, const uint6
 int abo_map_pe(void *mapper, int mode, uint64_t n, const char *blob1, const uint64_t *off1,
                const char *blob2, const uint64_t *off2, abo_pair *out_pair, abo_hit *out_se1,
                abo_hit *out_se2, uint32_t *cig1, uint32_t *cig2, uint32_t cig_stride,
-               uint32_t *cig_n1, uint32_t *cig_n2, unsigned threads, uint64_t *work9) {
+               uint32_t *cig_n1, uint32_t *cig_n2, unsigned threads, uint64_t *work) {
   MapperBox *b = static_cast<MapperBox *>(mapper);
   std::atomic<int> bad{0};
   std::vector<Work> works(std::max(1u, threads));
@@ -192,11 +194,11 @@ int abo_map_pe(void *mapper, int mode, uint64_t n, const char *blob1, const uint
   for (unsigned t = 0; t < nt; ++t)
     th.emplace_back(shard, t, n * t / nt, n * (t + 1) / nt);
   for (auto &x : th) x.join();
-  if (work9) {
+  if (work) {
     for (const Work &w : works) {
-      const uint64_t v[9] = {w.reads, w.seed_iters, w.search_probes, w.candidates, w.words,
-                             w.set_updates, w.aligns, w.aligns_tb, w.dp_cells};
-      for (int k = 0; k < 9; ++k) work9[k] += v[k];
+      const uint64_t v[kWorkValues] = {w.reads, w.seed_iters, w.search_probes, w.candidates, w.words, w.set_updates,
+                                       w.aligns, w.aligns_tb, w.dp_cells, w.blank_probes2, w.blank_probes3};
+      for (int k = 0; k < kWorkValues; ++k) work[k] += v[k];
     }
   }
   if (bad) { g_err = "oracle shard failed"; return -1; }

@@ -361,6 +361,13 @@ struct Mapper::Impl {
     return lo;
   }
 
+  // the letter a probe reads: p bases after index entry gp; a blank nibble is tallied
+  static u8 probed(const u64 *g, u32 gp, u32 p, u64 &blank) {
+    const u8 nib = gnib(g, static_cast<u64>(gp) + p);
+    blank += nib == 0;
+    return nib;
+  }
+
   // src/abismal.cpp:1163-1194: follow the read's 2-letter symbols past the
   // hashed prefix while the bucket is too big
   u32 narrow2(const u8 *q, u32 limit, const u32 *&lo, const u32 *&hi) {
@@ -369,7 +376,7 @@ struct Mapper::Impl {
     const u32 *plo = lo, *phi = hi;
     for (; p != limit && (hi - lo) > static_cast<std::ptrdiff_t>(par.max_candidates); ++p) {
       plo = lo; phi = hi;
-      const u32 *ones = first_not(lo, hi, [&](u32 gp) { return bit2(gnib(g, static_cast<u64>(gp) + p)) < 1u; });
+      const u32 *ones = first_not(lo, hi, [&](u32 gp) { return bit2(probed(g, gp, p, work.blank_probes2)) < 1u; });
       if (bit2(q[p])) lo = ones; else hi = ones;
     }
     if (lo == hi) { --p; lo = plo; hi = phi; }
@@ -384,8 +391,8 @@ struct Mapper::Impl {
     const u32 *plo = lo, *phi = hi;
     for (; p != limit && (hi - lo) > static_cast<std::ptrdiff_t>(par.max_candidates); ++p) {
       plo = lo; phi = hi;
-      const u32 *b1 = first_not(lo, hi, [&](u32 gp) { return sortsym3(gnib(g, static_cast<u64>(gp) + p), cv) < mid_sym; });
-      const u32 *b2 = first_not(lo, hi, [&](u32 gp) { return sortsym3(gnib(g, static_cast<u64>(gp) + p), cv) < top_sym; });
+      const u32 *b1 = first_not(lo, hi, [&](u32 gp) { return sortsym3(probed(g, gp, p, work.blank_probes3), cv) < mid_sym; });
+      const u32 *b2 = first_not(lo, hi, [&](u32 gp) { return sortsym3(probed(g, gp, p, work.blank_probes3), cv) < top_sym; });
       const u32 sym = sortsym3(q[p], cv);
       if (sym == 0) hi = b1;
       else if (sym == mid_sym) { lo = b1; hi = b2; }

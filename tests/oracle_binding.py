@@ -15,7 +15,7 @@ CLI = os.path.join(ORACLE_DIR, "_build", "abismal_oracle")
 HIT_DTYPE = np.dtype([("diffs", "<i2"), ("flags", "<u2"), ("pos", "<u4")])
 PAIR_DTYPE = np.dtype([("aln_score", "<i2"), ("reserved", "<i2"), ("r1", HIT_DTYPE), ("r2", HIT_DTYPE)])
 WORK_KEYS = ["reads", "seed_iters", "search_probes", "candidates", "words", "set_updates", "aligns",
-             "aligns_tb", "dp_cells"]
+             "aligns_tb", "dp_cells", "blank_probes2", "blank_probes3"]
 
 
 def build_oracle():
@@ -85,7 +85,7 @@ class Oracle:
         res = np.zeros(n, dtype=HIT_DTYPE)
         cig = np.zeros(max(1, n * cig_stride), dtype=np.uint32)
         cig_n = np.zeros(n, dtype=np.uint32)
-        work = np.zeros(9, dtype=np.uint64)
+        work = np.zeros(len(WORK_KEYS), dtype=np.uint64)
         try:
             self._chk(self.lib.abo_map_se(mp, mode, n, blob.ctypes.data, off.ctypes.data, res.ctypes.data,
                                           cig.ctypes.data, cig_stride, cig_n.ctypes.data, threads,
@@ -110,7 +110,7 @@ class Oracle:
         c2 = np.zeros(max(1, n * st), dtype=np.uint32)
         n1 = np.zeros(n, dtype=np.uint32)
         n2 = np.zeros(n, dtype=np.uint32)
-        work = np.zeros(9, dtype=np.uint64)
+        work = np.zeros(len(WORK_KEYS), dtype=np.uint64)
         try:
             self._chk(self.lib.abo_map_pe(mp, mode, n, b1.ctypes.data, o1.ctypes.data, b2.ctypes.data,
                                           o2.ctypes.data, pairs.ctypes.data, se1.ctypes.data, se2.ctypes.data,

@@ -187,3 +187,173 @@ def mutated_pairs(fasta, n, L, seed, mut=0.02, bis=0.95, frag=(120, 600)):
         out1.append(bytes(a))
         out2.append(bytes(b))
     return out1, out2
+
+
+# ---- repeat copies cut short by N runs: bucket narrowing where the probed letters are blank -----------------------------
+def repeats_against_n_runs(path, seed=17, n_chroms=2, chrom_len=130_000, n_full=160, n_trunc=40, fwd_frac=0.85,
+                           div=(0.01, 0.02), fam_len=300, run_len=300, unit=10):
+    """One repeat family of fam_len bases in n_full whole copies at 1-2 % divergence, mostly on one strand so that a
+    seed inside the family finds a bucket of more than 100 entries; n_trunc copies cut short -- the first t bases of
+    the oriented family, t spread over 30 ... fam_len - 10, then run_len N (more than 256: the indexer leaves the run
+    blank) -- so that the index entry o bases into such a copy has blank letters from depth t - o on and lies in the
+    bucket of the whole copies' entries at family offset o; one whole copy on the genome's last bases (its entries run
+    into the end padding); and one whole copy with 40 N inside (a short run, which the indexer fills: the control).
+    Returns the layout the read generators below cut from: {"fam", "full": [(chrom, at, strand)], "trunc": [(chrom, at,
+    strand, t)], "last": (chrom, at), "filled": (chrom, at)}; strand 1 = the family's reverse complement."""
+    rng = np.random.default_rng(seed)
+    fam = _n_run_family(rng, fam_len, unit)
+    slot = 2 * fam_len + run_len + 50  # a copy, its run and background between neighbours
+    per = (chrom_len - 2 * slot) // slot
+    assert n_chroms * per >= n_full + n_trunc + 1, "not enough room for the copies"
+    slots = [(c, slot + k * slot) for c in range(n_chroms) for k in range(per)]
+    order = rng.permutation(len(slots))
+    seqs = [ACGT[rng.integers(0, 4, chrom_len)].copy() for _ in range(n_chroms)]
+
+    def oriented(strand):
+        return COMP[fam[::-1]] if strand else fam
+
+    def diverged(piece):
+        piece = piece.copy()
+        m = rng.random(len(piece)) < rng.uniform(*div)
+        piece[m] = ACGT[rng.integers(0, 4, int(m.sum()))]
+        return piece
+
+    lay = {"fam": fam, "full": [], "trunc": [], "fam_len": fam_len, "run_len": run_len}
+    k = 0
+    for _ in range(n_full):
+        c, at = slots[order[k]]; k += 1
+        strand = int(rng.random() >= fwd_frac)
+        seqs[c][at:at + fam_len] = diverged(oriented(strand))
+        lay["full"].append((c, at, strand))
+    for j in range(n_trunc):
+        c, at = slots[order[k]]; k += 1
+        strand = int(rng.random() >= fwd_frac)
+        t = 30 + (j * (fam_len - 40)) // max(1, n_trunc - 1)
+        seqs[c][at:at + t] = diverged(oriented(strand))[:t]
+        seqs[c][at + t:at + t + run_len] = ord("N")
+        lay["trunc"].append((c, at, strand, t))
+    c, at = slots[order[k]]
+    piece = diverged(fam)
+    piece[120:160] = ord("N")
+    seqs[c][at:at + fam_len] = piece
+    lay["filled"] = (c, at)
+    seqs[-1][chrom_len - fam_len:] = diverged(fam)
+    lay["last"] = (n_chroms - 1, chrom_len - fam_len)
+    with open(path, "wb") as f:
+        for c, seq in enumerate(seqs):
+            f.write(b">chr%d\n" % (c + 1))
+            f.write(b"\n".join(bytes(seq[i:i + 70]) for i in range(0, chrom_len, 70)) + b"\n")
+    return lay
+
+
+def _n_run_family(rng, fam_len, unit):
+    """The family: its first half repeats one random unit, its second half one purine-only unit.  The indexer keeps one
+    position in twenty, each copy its own, so a family without inner structure would spread 160 copies over buckets of a
+    dozen entries; a repeated unit brings every kept position of every copy into one of `unit` buckets per table.  And a
+    position goes to the 2-letter table OR to the 3-letter ones, whichever buckets are emptier: the purine half (one 2-letter
+    bucket for all of it) is what puts entries, whole and cut short, into the 3-letter tables."""
+    half = fam_len // 2
+    a = np.resize(ACGT[rng.integers(0, 4, unit)], half)
+    b = np.resize(np.frombuffer(b"AG", dtype=np.uint8)[rng.integers(0, 2, unit)], fam_len - half)
+    return np.concatenate([a, b])
+
+
+def _n_run_fragments(lay, chroms, L, rng, per_copy, frag):
+    """Fragments (top-strand sequence as uint8 arrays) whose FIRST L bases are the read the issue is about:
+    kind a: cut from a whole copy so that the seeds of the read's first half fall on the family offsets 25 ... 45 bases before
+            the place where a cut-short copy of the same orientation ends (their buckets hold that copy's blank-tailed entries);
+    kind b: cut from a cut-short copy, the read ending on the last base before the run (returned reversed: see below);
+    kind c: starting inside a cut-short copy and continuing past the cut with the family's sequence, as the run were not there.
+    Every fragment is (kind, array, flip) with the read of interest = array[:L] if not flip, else the last L bases."""
+    fam_len = lay["fam_len"]
+    out = []
+    by_strand = {s: [x for x in lay["full"] if x[2] == s] for s in (0, 1)}
+    for (c, at, strand, t) in lay["trunc"]:
+        fam = COMP[lay["fam"][::-1]] if strand else lay["fam"]
+        for _ in range(per_copy):
+            flen = int(rng.integers(max(frag[0], L), frag[1]))
+            # a: a whole copy of the same orientation
+            cc, fat, _s = by_strand[strand][int(rng.integers(0, len(by_strand[strand])))] if by_strand[strand] else lay["full"][0]
+            lo, hi = max(0, t - 45 - L // 2 + 1), max(0, min(fam_len - L, t - 25))
+            s = int(rng.integers(min(lo, hi), hi + 1))
+            out.append(("a", chroms[cc][fat + s: fat + s + flen].copy(), False))
+            # b: ends on the last base before the run
+            end = at + t
+            out.append(("b", chroms[c][end - flen: end].copy(), True))
+            # c: continues past the cut with family sequence (and background after the family's end)
+            k = int(rng.integers(25, max(26, min(t, L - 20))))
+            piece = np.concatenate([chroms[c][at + t - k: at + t], fam[t:]])[:L]
+            if len(piece) < L:
+                piece = np.concatenate([piece, ACGT[rng.integers(0, 4, L - len(piece))]])
+            up = chroms[c][at + t - k - (flen - L): at + t - k]
+            out.append(("c", np.concatenate([up, piece]), True))
+    # the copy on the genome's last bases, and the copy with the filled run
+    c, at = lay["last"]
+    for _ in range(2 * per_copy):
+        flen = int(rng.integers(max(frag[0], L), frag[1]))
+        out.append(("b", chroms[c][len(chroms[c]) - flen:].copy(), True))
+    c, at = lay["filled"]
+    for _ in range(2 * per_copy):
+        flen = int(rng.integers(max(frag[0], L), frag[1]))
+        s = int(rng.integers(0, 100))
+        out.append(("a", chroms[c][at + s: at + s + flen].copy(), False))
+    return out
+
+
+def _bisulfite(s, rng, ga, bis):
+    src, dst = (ord("G"), ord("A")) if ga else (ord("C"), ord("T"))
+    s = s.copy()
+    s[(s == src) & (rng.random(len(s)) < bis)] = dst
+    return s
+
+
+def _sprinkle(s, rng, mut):
+    s = s.copy()
+    m = (rng.random(len(s)) < mut) & (s != ord("N"))
+    s[m] = ACGT[rng.integers(0, 4, int(m.sum()))]
+    return s
+
+
+def reads_against_n_runs(lay, fasta, L, seed, mode=0, per_copy=2, background=60, mut=0.005, bis=0.95):
+    """Single-end reads for repeats_against_n_runs (kinds a, b, c of _n_run_fragments, either strand, plus random background);
+    mode 0: C->T converted, 1: G->A, 2: half and half.  Apply trim_like_readloader afterwards."""
+    rng = np.random.default_rng(seed)
+    chroms = read_chroms(fasta)
+    reads = []
+    for kind, f, flip in _n_run_fragments(lay, chroms, L, rng, per_copy, (L, L + 1)):
+        s = f[-L:] if flip else f[:L]
+        s = _sprinkle(s, rng, mut)
+        if rng.random() < 0.5:
+            s = COMP[s[::-1]]
+        ga = mode == 1 or (mode == 2 and rng.random() < 0.5)
+        reads.append(bytes(_bisulfite(s, rng, ga, bis)))
+    pb = {0: 0.0, 1: 1.0, 2: 0.5}[mode]
+    return reads + mutated_reads(fasta, background, L, seed + 1, pbat_frac=pb)
+
+
+def pairs_against_n_runs(lay, fasta, L, seed, per_copy=2, background=100, unmated=12, mut=0.005, bis=0.95, frag=(160, 420)):
+    """Pairs for repeats_against_n_runs: one end is a read of kind a, b or c, its mate comes from the same fragment's other
+    end; `unmated` pairs have their ends on different chromosomes (fallback hits only); plus random background.  Conversion
+    as mutated_pairs: C->T on the fragment's strand.  Apply trim_like_readloader afterwards."""
+    rng = np.random.default_rng(seed)
+    chroms = read_chroms(fasta)
+    r1, r2 = [], []
+
+    def add(f):
+        f = _bisulfite(_sprinkle(f, rng, mut), rng, False, bis)
+        r1.append(bytes(f[:L]))
+        r2.append(bytes(COMP[f[::-1]][:L]))
+
+    frags = _n_run_fragments(lay, chroms, L, rng, per_copy, (max(frag[0], L + 20), frag[1]))
+    for kind, f, flip in frags:
+        add(COMP[f[::-1]] if rng.random() < 0.5 else f)
+    for k in range(unmated):  # a read of interest with an end from elsewhere
+        kind, f, flip = frags[int(rng.integers(0, len(frags)))]
+        s = f[-L:] if flip else f[:L]
+        ch = chroms[k % len(chroms)]
+        at = (2 * lay["fam_len"] + lay["run_len"] + 50) * (3 + k) - 320  # (background between two copies' slots)
+        other = ch[at:at + L]
+        r1.append(bytes(_bisulfite(s, rng, False, bis)))
+        r2.append(bytes(_bisulfite(other, rng, True, bis)))
+    b1, b2 = mutated_pairs(fasta, background, L, seed + 1, frag=(max(120, L), 600))
+    return r1 + b1, r2 + b2

@@ -249,10 +249,11 @@ def test_pairs_at_the_edges_of_n_runs(n_run_bed, L):
     record-fed kernel's narrowing probes read letters from the records and go to the nibble array where a record's N flag
     is set; without records (or with records too short: 108 for ends of 150) the probes and the four-lane filter read the
     planes, and ends of 250 and 300 take eight-lane groups.
-    What this does NOT reach: these ends stop before the run and no repeat lies against it, so no bucket that is narrowed
-    (more than max_candidates entries) holds an entry whose probed letters lie inside the run.  A pair-kernel build whose
-    record_nibble ignores the records' N flag passes this test, as it passes test_windows_that_reach_into_an_n_run; the
-    test guards the filters and the lane groups at the runs' edges, not that fallback of the narrowing probes."""
+    These ends stop before the run and no repeat lies against it, so no bucket that is narrowed (more than max_candidates
+    entries) holds an entry whose probed letters lie inside the run: this test guards the filters and the lane groups at
+    the runs' edges.  The narrowing probes' way back to the nibble array (record_nibble where a record's N flag is set,
+    narrow_direct's `ok`) is reached by tests/test_gpu_narrowing_at_n_runs.py: tests/hip/narrow_check.hip on the
+    functions themselves, and a repeat family with copies cut short by N runs end to end."""
     b = n_run_bed
     r1, r2 = synth.pairs_at_n_runs(synth.read_chroms(b.fa), (L,), seed=4 + L, mirrored=True, straddle=True, unmated=True)
     orc = b.map_oracle(r1, r2, 0)
