@@ -9,9 +9,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SE_T_RICH, SE_A_RICH, SE_RANDOM = 0, 1, 2
 PE_NORMAL, PE_PBAT, PE_RANDOM = 0, 1, 2
 RECORDS_SAM, RECORDS_BAM = 0, 1
+INFLATE_OK, INFLATE_HEADER, INFLATE_DATA, INFLATE_SIZE, INFLATE_CRC = 0, 1, 2, 3, 4
+ERR_INFLATE = -3
 
 HIT_DTYPE = np.dtype([("diffs", "<i2"), ("flags", "<u2"), ("pos", "<u4")])
 PAIR_DTYPE = np.dtype([("aln_score", "<i2"), ("reserved", "<i2"), ("r1", HIT_DTYPE), ("r2", HIT_DTYPE)])
+BGZF_BLOCK_DTYPE = np.dtype([("at", "<u8"), ("text_at", "<u8"), ("len", "<u4"), ("text_len", "<u4")])  # abm_bgzf_block
 
 EXPORTED_SYMBOLS = [
     "abm_last_error", "abm_default_params", "abm_index_open", "abm_index_close",
@@ -22,6 +25,7 @@ EXPORTED_SYMBOLS = [
     "abm_device_count", "abm_host_alloc", "abm_host_free", "abm_index_set_seed_extension", "abm_index_set_max_candidates", "abm_index_set_direct_narrowing", "abm_ctx_seed_extension", "abm_ctx_rebuild_seed_extension", "abm_device_numa_node",
     "abm_ctx_set_pe_split", "abm_ctx_pe_split_stats", "abm_ctx_pe_timed_launches", "abm_ctx_set_pair_phases", "abm_device_memory", "abm_ctx_pe_footprint", "abm_index_set_seed_extension_cap", "abm_ctx_pinned_bytes", "abm_ctx_set_sam_tails", "abm_ctx_slice_sam_tails", "abm_ctx_pe_sam_tails", "abm_ctx_set_record_format",
     "abm_index_set_window_records", "abm_ctx_window_records",
+    "abm_bgzf_scan", "abm_inflater_create", "abm_inflater_destroy", "abm_inflate_bgzf", "abm_inflate_bgzf_device",
 ]
 
 
@@ -107,6 +111,12 @@ def load_library():
                                      vp, vp, vp, vp, C.c_uint64]
     lib.abm_map_pe_device.argtypes = [vp, C.c_int, C.POINTER(Params), C.c_uint64, vp, vp, vp, vp, C.c_uint32,
                                       vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp]
+    if hasattr(lib, "abm_inflate_bgzf"):  # (absent from older builds loaded through ABISMAL_AMD_LIB)
+        lib.abm_bgzf_scan.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        lib.abm_inflater_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        lib.abm_inflater_destroy.argtypes = [vp]
+        lib.abm_inflate_bgzf.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_uint64, vp]
+        lib.abm_inflate_bgzf_device.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_uint64, vp, vp]
     _lib = lib
     return lib
 
@@ -133,6 +143,67 @@ def index_build(fasta, out, threads=0, targets=None, window=20):
         _check(load_library().abm_index_build_opts(os.fsencode(fasta), os.fsencode(targets or ""), window, os.fsencode(out), threads))
     else:
         _check(load_library().abm_index_build(os.fsencode(fasta), os.fsencode(out), threads))
+
+
+def bgzf_scan(data):
+    """abm_bgzf_scan: the blocks of BGZF data (bytes) as an array of BGZF_BLOCK_DTYPE -- one per block, blocks without
+    text included, the texts laid end to end -- and the text's length"""
+    lib = load_library()
+    buf = np.frombuffer(data, dtype=np.uint8)
+    n, text = C.c_uint64(), C.c_uint64()
+    _check(lib.abm_bgzf_scan(buf.ctypes.data if len(buf) else None, len(buf), None, 0, C.byref(n), C.byref(text)))
+    blocks = np.zeros(int(n.value), dtype=BGZF_BLOCK_DTYPE)
+    _check(lib.abm_bgzf_scan(buf.ctypes.data if len(buf) else None, len(buf), blocks.ctypes.data, len(blocks), C.byref(n), C.byref(text)))
+    return blocks, int(text.value)
+
+
+class Inflater:
+    """abm_inflater_create / abm_inflater_destroy + abm_inflate_bgzf: BGZF blocks inflated on the device"""
+
+    def __init__(self, device=0):
+        self._lib = load_library()
+        h = C.c_void_p()
+        _check(self._lib.abm_inflater_create(int(device), C.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if self.handle:
+            self._lib.abm_inflater_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def inflate(self, data, blocks=None, text_bytes=None):
+        """abm_inflate_bgzf over `data` (bytes).  blocks: an array of BGZF_BLOCK_DTYPE (None: bgzf_scan(data));
+        text_bytes: the text buffer's size (None: where the last text range ends).  Returns (text, status[u8]); a block
+        that did not inflate shows in its status (ABM_ERR_INFLATE does not raise), any other failure raises."""
+        if blocks is None:
+            blocks, text_bytes = bgzf_scan(data)
+        blocks = np.ascontiguousarray(blocks, dtype=BGZF_BLOCK_DTYPE)
+        if text_bytes is None:
+            text_bytes = int((blocks["text_at"] + blocks["text_len"]).max()) if len(blocks) else 0
+        buf = np.frombuffer(data, dtype=np.uint8)
+        text = np.zeros(max(1, text_bytes), dtype=np.uint8)
+        status = np.zeros(max(1, len(blocks)), dtype=np.uint8)
+        rc = self._lib.abm_inflate_bgzf(self.handle, buf.ctypes.data if len(buf) else None, len(buf), blocks.ctypes.data if len(blocks) else None,
+                                        len(blocks), text.ctypes.data, text_bytes, status.ctypes.data)
+        if rc != 0 and rc != ERR_INFLATE:
+            _check(rc)
+        return text[:text_bytes].tobytes(), status[:len(blocks)]
+
+    def inflate_device(self, d_comp, comp_bytes, d_blocks, n_blocks, d_text, text_bytes, d_status, stream=0):
+        """abm_inflate_bgzf_device: all d_* are integer device addresses (e.g. tensor.data_ptr()); not synchronised"""
+        _check(self._lib.abm_inflate_bgzf_device(self.handle, d_comp, comp_bytes, d_blocks, n_blocks, d_text, text_bytes, d_status, stream))
 
 
 # letters of the seed-extension tables that Index() asks for when its caller does not say: None = the library's

@@ -109,6 +109,9 @@ template <class T> struct HostBuf {
 
 }  // namespace
 
+// (abm_inflate.hip: the other translation unit whose entry points leave their reason in abm_last_error())
+namespace abm { void set_last_error(const std::string &what) { g_error = what; } }
+
 // the index arrays resident on one device, shared by every context created on it
 struct DeviceReplica {
   void *arena = nullptr;  // one allocation holding the seven index arrays

@@ -134,6 +134,7 @@ constexpr unsigned kPeDeviceSamWorkers = 0;
 // until device pieces are measured end to end at scale (40 M x 100 bp and 2 M pairs 2 x 150 at -t 2 / 4 / 16, three
 // interleaved runs each: DESIGN.md 4.5); ABM_CLI_DEVICE_SAM=1 turns them on.
 constexpr unsigned kSeDeviceBamWorkers = 0, kPeDeviceBamWorkers = 0;
+std::atomic<uint64_t> g_inflate_device_blocks{0}, g_inflate_host_blocks{0}, g_inflate_fallback_blocks{0};  // BGZF blocks of the input by who inflated them (fallback: the device rejected it, the host did not)
 std::atomic<uint64_t> g_device_records{0}, g_host_records{0};  // SAM / BAM records whose text the kernels / the formatters wrote
 
 // every ABM_CLI_* number: a positive value of the variable, else the default
@@ -162,6 +163,7 @@ struct RunPlan {
   uint64_t rec_bytes = 0;    // bytes per record of the first file (0: unknown)
   size_t reserve_reads = 0;
   bool stream_slices = false, device_sam = false;
+  bool device_inflate = false;  // BGZF input: the workers inflate a chunk's blocks on the run's GPUs (ABM_CLI_DEVICE_INFLATE)
   int pe_text_per_gpu = 0;   // paired: contexts per GPU whose batches carry SAM text from the device
   int se_mode = 0, pe_mode = 0;
   abm_params par;
@@ -283,6 +285,10 @@ RunPlan make_plan(const Options &opt, const Topology &topo, const CpuQuota &quot
   }
   if (all_bgzf && !env_set("ABM_CLI_NO_BGZF")) p.input = InputKind::Bgzf;
   else if (all_plain) p.input = env_set("ABM_CLI_NO_MMAP") ? InputKind::PlainPread : InputKind::PlainMapped;
+  // where BGZF blocks are inflated: ABM_CLI_DEVICE_INFLATE=1 on the run's GPUs (every host worker has an inflater on one
+  // of them), =0 on the host; the host is the default.  Virtual GPUs have no device; other input ignores it.
+  const char *where = std::getenv("ABM_CLI_DEVICE_INFLATE");
+  p.device_inflate = where && where[0] == '1' && p.input == InputKind::Bgzf && !p.virtual_gpus;
   p.n_regions = std::max(1, opt.out_parts);
   if (p.n_regions > 1 && p.input != InputKind::PlainMapped && p.input != InputKind::PlainPread) throw std::runtime_error("-out-parts needs plain (seekable, uncompressed) FASTQ input");
   for (size_t e = 0; e < opt.reads.size(); ++e) {  // (a pipe is not read ahead of the run)
@@ -604,6 +610,7 @@ struct Pipeline {
   std::vector<RawPool> raw_pool;
   std::vector<LineFile> lf;
   bool count_gated = false;  // BGZF: inflating further ahead is on hold until slices have been written
+  std::vector<DeviceBgzf> inflaters;  // device inflate: one per host worker, dealt round the run's GPUs; empty otherwise
   std::vector<std::unique_ptr<Batch>> live_batches;
   int mappers_live;
   std::vector<unsigned> workers_on;
@@ -642,6 +649,10 @@ struct Pipeline {
       R.max_in_flight = std::max<size_t>(plan.max_reads_in_flight / plan.n_regions, 2 * plan.batch_reads);
     }
     for (unsigned t = 0; t < plan.n_host; ++t) ++workers_on[t % n_nodes];
+    if (plan.device_inflate) {
+      inflaters = std::vector<DeviceBgzf>(plan.n_host);
+      for (unsigned t = 0; t < plan.n_host; ++t) inflaters[t].open(plan.dev_of[t % static_cast<unsigned>(plan.n_gpus)]);
+    }
     // ---- output files.  A slice's place is fixed in slice order; its region's writer pwrite()s it.
     // (Writes to one file take its inode lock, so they run one at a time; copying into a shared mapping of the file
     // from all threads instead was measured 3x SLOWER -- page faults on the mapping contend far worse than the lock.)
@@ -928,18 +939,42 @@ struct Pipeline {
     e = best; k = lf[e].next_chunk++;
     return true;
   }
-  void count_chunk(size_t e, uint64_t k, std::vector<char> &buf) {  // the newlines of one chunk
+  // the newlines of one chunk; `dev`: the calling worker's inflater (device inflate), else null
+  void count_chunk(size_t e, uint64_t k, std::vector<char> &buf, DeviceBgzf *dev_of_worker) {
     const auto t0 = now();
     const uint64_t lo = lf[e].chunk_begin[k], hi = lf[e].chunk_begin[k + 1];
     if (lf[e].cmap) {  // BGZF: this chunk's blocks are inflated into their place in the text first
       thread_local BgzfInflater inf;
       LineFile &F = lf[e];
-      for (uint32_t b = F.chunk_first_block[k]; b < F.chunk_first_block[k + 1]; ++b) {
+      const uint32_t b0 = F.chunk_first_block[k], b1 = F.chunk_first_block[k + 1];
+      DeviceBgzf scratch;  // (host inflate: unused)
+      DeviceBgzf &dev = dev_of_worker ? *dev_of_worker : scratch;
+      dev.blocks.clear();
+      for (uint32_t b = b0; b < b1; ++b) {
         uint32_t data_off = 0;
         const uint32_t len = bgzf_block_length(F.cmap + F.block_at[b], F.csize - F.block_at[b], data_off);
         if (!len) throw std::runtime_error("corrupt BGZF block in " + opt.reads[e]);
         // (blocks without text were left out of the list: the next listed block begins where this one's text ends)
-        inf.block(F.cmap + F.block_at[b], len, data_off, const_cast<char *>(F.map) + F.block_text[b], static_cast<uint32_t>(F.block_text[b + 1] - F.block_text[b]));
+        const uint32_t text_len = static_cast<uint32_t>(F.block_text[b + 1] - F.block_text[b]);
+        if (plan.device_inflate) dev.blocks.push_back(abm_bgzf_block{F.block_at[b] - F.block_at[b0], F.block_text[b] - F.block_text[b0], len, text_len});
+        else inf.block(F.cmap + F.block_at[b], len, data_off, const_cast<char *>(F.map) + F.block_text[b], text_len);
+      }
+      if (!plan.device_inflate) g_inflate_host_blocks += b1 - b0;
+      else if (b1 > b0) {
+        // one call per chunk: the blocks go up, are inflated one wave each, and their text lands in its place
+        const abm_bgzf_block &last = dev.blocks.back();
+        const bool all_ok = dev.run(F.cmap + F.block_at[b0], last.at + last.len, const_cast<char *>(F.map) + F.block_text[b0], F.block_text[b1] - F.block_text[b0]);
+        uint32_t redone = 0;
+        for (uint32_t b = b0; !all_ok && b < b1; ++b) {
+          if (dev.status[b - b0] == ABM_INFLATE_OK) continue;
+          // a block the device rejected goes through the host's inflater: it ends the run with its message, or its text counts
+          uint32_t data_off = 0;
+          const uint32_t len = bgzf_block_length(F.cmap + F.block_at[b], F.csize - F.block_at[b], data_off);
+          inf.block(F.cmap + F.block_at[b], len, data_off, const_cast<char *>(F.map) + F.block_text[b], dev.blocks[b - b0].text_len);
+          ++redone;
+        }
+        g_inflate_fallback_blocks += redone;
+        g_inflate_device_blocks += b1 - b0 - redone;
       }
     }
     const char *base = lf[e].map ? lf[e].map + lo : nullptr;
@@ -1646,7 +1681,7 @@ struct Pipeline {
   }
 
   // host workers: -t of them, pinned node by node; each takes the most urgent task its node has, else another node's
-  void worker(int node) {
+  void worker(int node, unsigned id) {
     topo.pin(node, workers_on[node]);
     std::vector<char> count_buf;
     const bool count_first = plan.n_regions > 1;  // (the later regions cannot start before the whole input has been counted)
@@ -1677,7 +1712,7 @@ struct Pipeline {
             if (nq[node].waking > 0) --nq[node].waking;
           }
         }
-        if (to_count) count_chunk(ce, ck, count_buf);
+        if (to_count) count_chunk(ce, ck, count_buf, inflaters.empty() ? nullptr : &inflaters[id]);
         else if (to_format) format_task(to_format);
         else parse_slice(std::move(to_parse));
       }
@@ -1751,7 +1786,7 @@ struct Pipeline {
     std::vector<std::thread> threads;
     if (plan.plain()) for (int r = 0; r < plan.n_regions; ++r) threads.emplace_back(&Pipeline::cutter_plain, this, r);
     else threads.emplace_back(&Pipeline::cutter_stream, this);
-    for (unsigned t = 0; t < plan.n_host; ++t) threads.emplace_back(&Pipeline::worker, this, static_cast<int>(t % n_nodes));
+    for (unsigned t = 0; t < plan.n_host; ++t) threads.emplace_back(&Pipeline::worker, this, static_cast<int>(t % n_nodes), t);
     for (int slot = 0; slot < plan.n_gpus * plan.per_gpu; ++slot) threads.emplace_back(&Pipeline::mapper, this, slot);
     for (int r = 0; r < plan.n_regions; ++r) threads.emplace_back(&Pipeline::writer, this, r);
     {
@@ -1849,6 +1884,7 @@ void write_timing_file(const Options &opt, const RunPlan &plan, const Topology &
      << ", \"index_load_s\": " << rep.index_load_s << ", \"host_prepare_s\": " << pl.host_prepare_s << ", \"gpus\": " << plan.n_gpus << ", \"mappers_per_gpu\": " << plan.per_gpu
      << ", \"sam_text_by\": \"" << (plan.device_sam ? "device" : "host") << "\", \"sam_records\": {\"device\": " << g_device_records.load() << ", \"host\": " << g_host_records.load() << "}, \"pe_text_contexts_per_gpu\": " << (plan.paired && plan.device_sam ? plan.pe_text_per_gpu : 0) << ", \"window_records_serve_reads_up_to\": " << (ctxs.empty() ? 0u : abm_ctx_window_records(ctxs[0])) << ", \"host_threads\": " << plan.n_host << ", \"numa_nodes\": " << plan.n_nodes << ", \"pinned\": " << (topo.pinning ? "true" : "false")
      << ", \"out_parts\": " << plan.n_regions << ", \"out_bytes\": " << pl.out_bytes << ", \"batches\": " << pl.n_batches << ", \"max_lead_in_records\": " << pl.max_lead << ", \"region_lead_in_scanned_records\": " << pl.region_lead_scanned << ", \"region_lead_in_records\": " << pl.region_lead_records
+     << ", \"inflate\": {\"where\": \"" << (plan.device_inflate ? "device" : "host") << "\", \"device_blocks\": " << g_inflate_device_blocks.load() << ", \"host_blocks\": " << g_inflate_host_blocks.load() << ", \"fallback_blocks\": " << g_inflate_fallback_blocks.load() << "}"
      << ", \"batch_reads\": " << plan.batch_reads << ", \"host_ceiling\": " << (plan.virtual_gpus ? "true" : "false")
      << ", \"batches_per_gpu\": [";
   for (int g = 0; g < plan.n_gpus; ++g) tj << (g ? ", " : "") << pl.gpu_batches[g];
@@ -1958,15 +1994,57 @@ int main(int argc, char **argv) {
       return EXIT_SUCCESS;
     }
     if (cmd == "bgzf") {  // abismal-amd bgzf [-z n] <in> <out>: any file as BGZF blocks, the way -B output is compressed (a test hook)
+      // abismal-amd bgzf -d [-device k] <in> <out>: the other way round -- any BGZF file inflated whole, by the host's
+      // BgzfInflater, or with -device by abm_inflate_bgzf on that GPU; a damaged block ends it and is named by its offset
       std::vector<std::string> pos;
+      bool decompress = false;
+      int device = -1;
       for (int i = 2; i < argc; ++i) {
         if (std::string(argv[i]) == "-z" && i + 1 < argc) g_bgzf_level = std::max(0, std::min(9, std::atoi(argv[++i])));
+        else if (std::string(argv[i]) == "-d") decompress = true;
+        else if (std::string(argv[i]) == "-device" && i + 1 < argc) device = std::atoi(argv[++i]);
         else pos.push_back(argv[i]);
       }
-      if (pos.size() != 2) { std::cerr << "usage: abismal-amd bgzf [-z n] <in> <out>\n"; return EXIT_FAILURE; }
+      if (pos.size() != 2) { std::cerr << "usage: abismal-amd bgzf [-z n] <in> <out>\n       abismal-amd bgzf -d [-device k] <in> <out>\n"; return EXIT_FAILURE; }
       std::ifstream in(pos[0], std::ios::binary);
       if (!in) throw std::runtime_error("cannot open " + pos[0]);
       std::string raw((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>()), z;
+      if (decompress) {
+        const unsigned char *p = reinterpret_cast<const unsigned char *>(raw.data());
+        uint64_t n_blocks = 0, text_bytes = 0;
+        if (abm_bgzf_scan(p, raw.size(), nullptr, 0, &n_blocks, &text_bytes) != 0) throw std::runtime_error(std::string(abm_last_error()) + ": " + pos[0]);
+        std::vector<abm_bgzf_block> blocks(n_blocks);
+        if (abm_bgzf_scan(p, raw.size(), blocks.data(), n_blocks, &n_blocks, &text_bytes) != 0) throw std::runtime_error(abm_last_error());
+        std::string text(text_bytes, '\0');
+        const auto damaged = [&](const abm_bgzf_block &b, const std::string &why) {
+          return std::runtime_error("corrupt BGZF block at byte " + std::to_string(b.at) + " of " + pos[0] + " (" + why + ")");
+        };
+        if (device < 0) {
+          BgzfInflater inf;
+          for (const abm_bgzf_block &b : blocks) {
+            uint32_t data_off = 0;
+            if (bgzf_block_length(p + b.at, b.len, data_off) != b.len) throw damaged(b, "header");
+            try { inf.block(p + b.at, b.len, data_off, &text[b.text_at], b.text_len); }
+            catch (const std::exception &e) { throw damaged(b, e.what()); }
+          }
+        }
+        else {
+          DeviceBgzf dev;
+          dev.open(device);
+          for (size_t b0 = 0; b0 < blocks.size(); b0 += 2048) {  // (128 MB of text a call)
+            const size_t b1 = std::min(blocks.size(), b0 + 2048);
+            dev.blocks.assign(blocks.begin() + b0, blocks.begin() + b1);
+            for (abm_bgzf_block &b : dev.blocks) { b.at -= blocks[b0].at; b.text_at -= blocks[b0].text_at; }
+            const abm_bgzf_block &last = dev.blocks.back();
+            if (dev.run(p + blocks[b0].at, last.at + last.len, &text[0] + blocks[b0].text_at, last.text_at + last.text_len)) continue;
+            for (size_t b = b0; b < b1; ++b)
+              if (dev.status[b - b0] != ABM_INFLATE_OK) throw damaged(blocks[b], "device status " + std::to_string(dev.status[b - b0]));
+          }
+        }
+        std::ofstream out(pos[1], std::ios::binary);
+        out.write(text.data(), static_cast<std::streamsize>(text.size()));
+        return out ? EXIT_SUCCESS : EXIT_FAILURE;
+      }
       bgzf_compress(raw, z);
       static const unsigned char eof_block[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
       z.append(reinterpret_cast<const char *>(eof_block), 28);

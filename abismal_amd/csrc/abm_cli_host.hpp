@@ -172,6 +172,27 @@ struct BgzfInflater {
   }
 };
 
+// one thread's inflater on a GPU (the C ABI's abm_inflater: its own stream, device buffers and pinned staging), with the
+// descriptors and statuses of its current call
+struct DeviceBgzf {
+  abm_inflater *inf = nullptr;
+  std::vector<abm_bgzf_block> blocks;
+  std::vector<uint8_t> status;
+  DeviceBgzf() = default;
+  DeviceBgzf(const DeviceBgzf &) = delete;
+  ~DeviceBgzf() { if (inf) abm_inflater_destroy(inf); }
+  void open(int device) {
+    if (!inf && abm_inflater_create(device, &inf) != 0) throw std::runtime_error(abm_last_error());
+  }
+  // `blocks` (offsets relative to comp and text) -> text; true: every block inflated, false: see `status`
+  bool run(const unsigned char *comp, uint64_t comp_bytes, char *text, uint64_t text_bytes) {
+    status.assign(blocks.size(), 0);
+    const int rc = abm_inflate_bgzf(inf, comp, comp_bytes, blocks.data(), static_cast<uint32_t>(blocks.size()), text, text_bytes, status.data());
+    if (rc != 0 && rc != ABM_ERR_INFLATE) throw std::runtime_error(abm_last_error());
+    return rc == 0;
+  }
+};
+
 // a mapped input file that shrinks under the run (truncated, a network file system losing it) faults with SIGBUS
 void install_sigbus_handler() {
   struct sigaction sa;

@@ -359,6 +359,49 @@ int abm_ctx_take_kernel_times(abm_ctx *ctx, double *ms_out, uint64_t capacity, u
  * device once. */
 int abm_stats_allreduce(abm_ctx *const *ctxs, int n_ctx, uint64_t *const *counters);
 
+/* BGZF input inflated on the device (no reference counterpart: the reference reads its FASTQ through htslib on the host,
+ * src/abismal.cpp:150-209).  bgzip and the base-callers write compressed FASTQ as BGZF (SAM specification 4.1):
+ * independent gzip members of at most 64 KB whose headers say how long they are -- so a batch of blocks is inflated as a
+ * batch of reads is mapped, one wavefront per block (RFC 1951: stored, fixed and dynamic blocks; the member's ISIZE and
+ * CRC-32 are checked on the device too).
+ * A block descriptor: the member is bytes [at, at + len) of the compressed buffer and its text is bytes
+ * [text_at, text_at + text_len) of the text buffer; len and text_len are at most 65536.  Each block gets a status byte. */
+typedef struct abm_inflater abm_inflater; /* one stream on one GPU + its grow-only device buffers and pinned staging */
+typedef struct { uint64_t at; uint64_t text_at; uint32_t len; uint32_t text_len; } abm_bgzf_block;
+enum {
+  ABM_INFLATE_OK = 0, /* the block inflated */
+  ABM_INFLATE_HEADER, /* not a BGZF header, or a field (XLEN, a subfield, BSIZE, the descriptor) that points outside the block */
+  ABM_INFLATE_DATA,   /* an invalid deflate stream: block type 3, stored LEN / NLEN that disagree, over-subscribed or
+                         illegally incomplete code lengths, a repeat code with nothing to repeat, literal/length symbols
+                         286 / 287, distance symbols 30 / 31, a distance beyond the text so far, a stream past the block's end */
+  ABM_INFLATE_SIZE,   /* the text produced is not text_len bytes, or the member's ISIZE is not text_len */
+  ABM_INFLATE_CRC     /* checksum mismatch */
+};
+#define ABM_ERR_INFLATE (-3)
+/* Host: walks the headers of `bytes` bytes of BGZF -- one descriptor per block (blocks without text included), the texts
+ * laid end to end from 0.  out may be NULL (capacity 0) to count: *n_blocks and *text_bytes are always the file's.  A
+ * header that is not BGZF's, or a file that ends inside a header or a block, is an error (< 0) that names the offset;
+ * ABM_ERR_CAPACITY if there are more blocks than `capacity`. */
+int abm_bgzf_scan(const void *comp, uint64_t bytes, abm_bgzf_block *out, uint64_t capacity, uint64_t *n_blocks, uint64_t *text_bytes);
+/* An inflater is independent of any abm_ctx; several on one device run side by side, each on its own stream.  Calls on one
+ * inflater are serialised.  Without a HIP device the call fails with a message: the library has no CPU fallback. */
+int abm_inflater_create(int device, abm_inflater **out);
+void abm_inflater_destroy(abm_inflater *inf);
+/* Host buffers (pageable is fine): upload, inflate, copy out; returns when the text is in `text`.
+ *   0                every block is ABM_INFLATE_OK
+ *   ABM_ERR_INFLATE  the call ran and some block's status is not: the texts of the OK blocks are valid, a failed block's
+ *                    range of `text` holds unspecified bytes, nothing outside the blocks' ranges is touched
+ *   other < 0        the call itself failed (abm_last_error()): a null pointer, a descriptor whose at + len exceeds
+ *                    comp_bytes or whose text_at + text_len exceeds text_bytes (checked before anything is launched), a
+ *                    HIP error.  Nothing was written. */
+int abm_inflate_bgzf(abm_inflater *inf, const void *comp, uint64_t comp_bytes, const abm_bgzf_block *blocks, uint32_t n_blocks,
+                     void *text, uint64_t text_bytes, uint8_t *status);
+/* The same with everything resident in HBM (d_* are device pointers, descriptors included), enqueued on `stream` (a
+ * hipStream_t; NULL = default stream) and not synchronised, as abm_map_se_device: returns 0 once enqueued, the outcome is
+ * d_status.  A descriptor that points outside comp_bytes / text_bytes gets ABM_INFLATE_HEADER from the kernel. */
+int abm_inflate_bgzf_device(abm_inflater *inf, const void *d_comp, uint64_t comp_bytes, const abm_bgzf_block *d_blocks, uint32_t n_blocks,
+                            void *d_text, uint64_t text_bytes, uint8_t *d_status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
