@@ -359,6 +359,10 @@ struct LaunchShape {
   abm::u32 eff_len, W, WB, GW, tb_extra, G, ctmp_cap;
   double size_frac;
 };
+// The inputs of the kernels' LDS layouts (abm_lds_layout.hpp).  se_device, pe_device and the long launches copy exactly
+// these fields into their argument blocks (a.max_len = s.eff_len, a.ctmp_cap = s.ctmp_cap, ...), so the layout a launcher
+// derives from its arguments (abm::lds_shape(a)) is the one planned here
+abm::LdsShape lds_shape_of(const LaunchShape &s) { return abm::LdsShape{s.W, s.WB, s.GW, s.eff_len, s.ctmp_cap, s.tb_extra}; }
 LaunchShape launch_shape(const abm_ctx *ctx, abm::u32 max_len, double valid_frac, ShapeKind kind) {
   LaunchShape s{};
   const bool lng = kind == ShapeKind::kLong;
@@ -436,7 +440,7 @@ abm::u32 se_text_stride(const abm_ctx *ctx, const LaunchShape &s, abm::u32 cig_s
   if (!ctx->sam_on || !host_results || !sliced) return 0;
   if (ctx->sam_format == ABM_RECORDS_BAM && ctx->phase_stamps) return 0;  // (the diagnostic builds write no BAM pieces; the pair kernels' write no records at all)
   const abm::u32 stride = ctx->sam_format == ABM_RECORDS_BAM ? bam_stride_for(s.eff_len, cig_stride) : sam_stride_for(ctx, s.eff_len, cig_stride);
-  return stride <= abm::sam_line_room(s.GW, s.tb_extra) ? stride : 0;
+  return stride <= abm::lds_table_room(s.GW, s.tb_extra) ? stride : 0;
 }
 
 // Every workspace se_device needs for n reads of one launch shape.  se_device and abm_ctx_reserve both size through
@@ -474,7 +478,7 @@ void se_long_reads(abm_ctx *ctx, const abm::SeArgs &main, uint64_t n, const char
   const abm::u32 cap2 = (s.ctmp_cap + 1) & ~1u;
   int waves = 0;
   if (count) {
-    waves = abm::se_long_resident_waves(s.W, s.WB, s.GW);
+    waves = abm::se_long_resident_waves(abm::se_lds_layout<abm::u32>(0, true, lds_shape_of(s)).bytes);
     if (waves <= 0) throw HipFail("map_se_long_kernel does not fit on this device (LDS)");
   }
   const abm::u32 round = 1024;
@@ -586,7 +590,7 @@ void se_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
   int waves;
   auto it = ctx->se_waves.find(key);
   if (it != ctx->se_waves.end()) waves = it->second;
-  else { waves = abm::se_resident_waves(s.W, s.WB, s.ctmp_cap, s.eff_len, s.size_frac); ctx->se_waves[key] = waves; }
+  else { waves = abm::se_resident_waves(abm::se_lds_layout<abm::u32>(0, false, abm::lds_shape(a)).bytes); ctx->se_waves[key] = waves; }
   if (waves <= 0) throw HipFail("map_se_kernel does not fit on this device (LDS/occupancy)");
   abm::u32 grid = static_cast<abm::u32>(waves);  // persistent: one wave per resident slot
   if (const char *e = experiment_env("ABM_GRID_WAVES")) grid = std::max(64, std::atoi(e));
@@ -594,7 +598,7 @@ void se_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
   a.drained = host.signal_drained ? ctx->drained : nullptr;
   timed_launch(ctx, st, [&] {
     a.next_read = fresh_counter(ctx, st);
-    HIPCHK(abm::launch_map_se(a, s.eff_len, grid, ctx->phase_stamps, st));
+    HIPCHK(abm::launch_map_se(a, grid, ctx->phase_stamps, st));
   });
   if (has_long) se_long_reads(ctx, a, n, d_blob, d_off, std::min<abm::u32>(max_len, abm::kMaxReadLen), params->valid_frac, host, st);
   HIPCHK(hipEventRecord(ctx->last_done, st));
@@ -707,7 +711,7 @@ void pe_tier2_reserve(abm_ctx *ctx, size_t waves) {
 struct PeLaunch { size_t lds; int wps, waves; };
 PeLaunch pe_whole_launch(const abm_ctx *ctx, const LaunchShape &s, uint64_t n, bool large, bool text) {
   PeLaunch l{};
-  l.lds = abm::pe_lds_bytes(s.W, s.WB, s.GW, s.ctmp_cap, s.eff_len, s.size_frac, large ? abm::kPeCapLarge : abm::kPeTier1Cap, large) + (text ? abm::kPeFinBytes : 0);
+  l.lds = abm::pe_lds_layout<abm::u32>(0, abm::kWhole, false, large, text, lds_shape_of(s), large ? abm::kPeCapLarge : abm::kPeTier1Cap).bytes;
   l.wps = abm::pe_waves_per_simd(l.lds, ctx->phase_stamps, s.G != 0);
   if (const char *e = experiment_env(large ? "ABM_PE_WPS2" : "ABM_PE_WPS")) { if (!ctx->phase_stamps && s.G != 0 && (e[0] == '3' || e[0] == '4')) l.wps = e[0] - '0'; }
   if (text) l.wps = abm::pe_text_waves_per_simd();  // (the text builds: launch_map_pe)
@@ -741,7 +745,7 @@ size_t pe_hand_entries(const abm_ctx *ctx, uint64_t n) {
 struct PeSeedLaunch { size_t lds; abm::u32 grid; };
 PeSeedLaunch pe_seed_launch(const LaunchShape &s, uint64_t n) {
   PeSeedLaunch l{};
-  l.lds = abm::pe_seed_lds_bytes(s.W, s.WB, s.eff_len, abm::kPeTier1Cap);
+  l.lds = abm::pe_lds_layout<abm::u32>(0, abm::kSeed, false, false, false, lds_shape_of(s), abm::kPeTier1Cap).bytes;
   const int waves = abm::pe_seed_resident_waves(l.lds, s.G != 0);
   l.grid = waves <= 0 ? 0u : static_cast<abm::u32>(std::min<uint64_t>(n, waves));
   return l;
@@ -753,7 +757,7 @@ PeSeedLaunch pe_seed_launch(const LaunchShape &s, uint64_t n) {
 abm::u32 pe_text_stride(const abm_ctx *ctx, const LaunchShape &s, abm::u32 cig_stride, bool host_results) {
   if (!ctx->sam_on || !host_results || ctx->phase_stamps || s.G == 0) return 0;
   const abm::u32 stride = ctx->sam_format == ABM_RECORDS_BAM ? bam_stride_for(s.eff_len, cig_stride) : pe_sam_stride_for(ctx, s.eff_len, cig_stride);
-  return stride <= abm::sam_line_room(s.GW, s.tb_extra) ? stride : 0;
+  return stride <= abm::lds_table_room(s.GW, s.tb_extra) ? stride : 0;
 }
 
 // What pe_device settles before it touches a buffer: the route through tier 1 (split by phase or not), the text slot, and the
@@ -820,7 +824,7 @@ void pe_long_pairs(abm_ctx *ctx, const abm::PeArgs &main, uint64_t n, const char
   if (count == 0) return;
   const LaunchShape s = launch_shape(ctx, max_len, valid_frac, ShapeKind::kLong);
   const abm::u32 cap2 = (s.ctmp_cap + 1) & ~1u;
-  const int waves = abm::pe_long_resident_waves(s.GW);
+  const int waves = abm::pe_long_resident_waves(abm::pe_lds_layout<abm::u32>(0, abm::kWhole, true, true, false, lds_shape_of(s), abm::kPeCapLarge).bytes);
   if (waves <= 0) throw HipFail("the paired-end long-end launch does not fit on this device (LDS)");
   const abm::u32 round = 256;  // (a round's packed encodings: 2 x 256 x 4 W words = 32 MB at the longest reads)
   for (abm::u32 at = 0; at < count; at += round) {
@@ -919,7 +923,6 @@ void pe_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
     a.sam_format = ctx->sam_format;
     ctx->pe_sam_pairs = n;
   }
-  const size_t fin_lds = text ? abm::kPeFinBytes : 0;
   arena_setup(ctx, a, host.host_results, st);
   const size_t events_before = ctx->events_used;
   a.cap = abm::kPeTier1Cap;
@@ -953,7 +956,7 @@ void pe_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
     timed_launch(ctx, st, [&] { HIPCHK(abm::launch_pe_seed(a, seed.lds, seed.grid, ctx->phase_stamps, st)); });
     // MATE, small lists (every list of the pair within kPeTier1Cap entries: LDS): sort, scoring, mating, tracebacks,
     // best_single, fallback -- instruction-bound, it overlaps with the other contexts' seed kernels
-    const size_t lds_m = abm::pe_mate_lds_bytes(s.W, s.GW, s.ctmp_cap, s.eff_len, s.size_frac, a.cap, false) + fin_lds;
+    const size_t lds_m = abm::pe_lds_layout<abm::u32>(0, abm::kMate, false, false, text, abm::lds_shape(a), a.cap).bytes;
     const int waves_m = abm::pe_mate_resident_waves(lds_m, false);
     if (waves_m <= 0) throw HipFail("map_pe_kernel (mate) does not fit on this device");
     a.order = nullptr;  // (in input order: the lists were handed over in whatever order the seed kernel finished them)
@@ -975,7 +978,7 @@ void pe_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
     a.work = ctx->work.p + 16;  // tier 2 tallies separately (abm_ctx_take_work_tiers)
     if (split) {
       // the pairs whose lists outgrew LDS inside the seed kernel's staging area: mated from global memory (nothing is seeded twice)
-      const size_t lds_mb = abm::pe_mate_lds_bytes(s.W, s.GW, s.ctmp_cap, s.eff_len, s.size_frac, a.cap, true) + fin_lds;
+      const size_t lds_mb = abm::pe_lds_layout<abm::u32>(0, abm::kMate, false, true, text, abm::lds_shape(a), a.cap).bytes;
       const int waves_mb = std::min(abm::pe_mate_resident_waves(lds_mb, true), t2.waves);  // (the two launches share the workspaces)
       if (waves_mb <= 0) throw HipFail("map_pe_kernel (mate, tier 2) does not fit on this device");
       HIPCHK(abm::launch_collect_big(ctx->need_big.p, ctx->cls.p, n, abm::kRouteBig, ctx->class33_b.p, ctx->subset_b.p, ctx->subset_count_b.p, st));

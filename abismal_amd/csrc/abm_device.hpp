@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "abm_lds_layout.hpp"
+
 namespace abm {
 
 using u8 = uint8_t;
@@ -26,8 +28,7 @@ constexpr u32 kLdsReadLen = 1024;  // reads up to this keep their traceback tabl
 constexpr u32 kMaxReadLen = 32766; // longest read mapped: the reference refuses reads of padding_size = 32767 bases or more
                                    // (src/abismal.cpp:179-185, src/AbismalIndex.hpp:93); longer single-end reads than
                                    // kLdsReadLen go through a launch of their own with that table in global memory
-constexpr u32 kMaxBand = 61;     // src/AbismalAlign.hpp:108,133
-constexpr u32 kSeCap = 50;       // src/abismal.cpp:448
+// (kMaxBand, kSeCap, kPlaneBlock: abm_lds_layout.hpp)
 constexpr u32 kPeCapSmall = 32, kPeCapLarge = 32u << 10;  // src/abismal.cpp:861-862
 
 constexpr u32 kFlagRC = 0x10, kFlagAmbig = 0x100, kFlagARich = 0x1000;
@@ -89,7 +90,6 @@ constexpr u32 kDirectMin = ABM_PE_DIRECT_MIN;
 #define ABM_SE_DIRECT_MIN 64  // (every range beyond max_candidates = 100: 10 M x 100 bp 433 ms at 64, 440 at 128, 455 at 256, 468 at 512; profiles/r05_exp_se_direct_threshold.log)
 #endif
 constexpr u32 kDirectMinSe = ABM_SE_DIRECT_MIN;
-constexpr u32 kPlaneBlock = 64;       // bases per bit-plane block
 constexpr u32 kPlaneLineBlocks = 8;   // blocks per 128-byte line
 constexpr u32 kPlaneChunkBits = 12;   // nmap: log2 of the bases per chunk
 constexpr u32 kPlaneReach = 512;      // >= the bases a window of the cooperative filter spans (reads up to 448 + slack)

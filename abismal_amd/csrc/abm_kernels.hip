@@ -149,32 +149,7 @@ __device__ __forceinline__ void map_se_body(const SeArgs &a) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int lane = lane_id();
   WaveLds lds;
-  lds.W = a.W;
-  lds.WB = a.WB;
-  lds.qpk = reinterpret_cast<u64 *>(smem);
-  lds.GW = a.GW;
-  lds.qbits = lds.qpk + 4 * a.W;
-  lds.MB = LONG ? 0u : (a.max_len + kPlaneBlock - 1) / kPlaneBlock;
-  lds.qmask = lds.qbits + 4 * a.WB;
-  lds.max_jobs = LONG ? 2u : kMaxJobs;
-  {
-    unsigned char *p = reinterpret_cast<unsigned char *>(lds.qmask + 4 * lds.MB * 4);
-    const u32 cap2 = (a.ctmp_cap + 1) & ~1u;
-    if (LONG) lds.ctmp = a.long_ctmp + static_cast<u64>(blockIdx.x) * cap2;
-    else { lds.ctmp = reinterpret_cast<u32 *>(p); p += cap2 * 4; }
-    lds.jpos = reinterpret_cast<u32 *>(p); p += kSeCap * 4;
-    lds.jdf = reinterpret_cast<u32 *>(p); p += kSeCap * 4;
-    lds.gwin = reinterpret_cast<u64 *>(p); p += lds.max_jobs * a.GW * 8;
-    lds.pcache = reinterpret_cast<u64 *>(p); p += (8u << kPosCacheBits) + (LONG ? 0u : a.tb_extra);
-    // the traceback table overlays window slots 1.. and the window cache (a traceback uses slot 0 only)
-    lds.tb = LONG ? a.long_tb + static_cast<u64>(blockIdx.x) * a.long_tb_bytes : reinterpret_cast<u8 *>(lds.gwin + a.GW);
-    lds.lbest = reinterpret_cast<int *>(p); p += 64 * 4;
-    lds.smark = reinterpret_cast<u32 *>(p); p += 128 * 4;
-    lds.sdelta = reinterpret_cast<u32 *>(p); p += 128 * 4;
-    lds.mark = reinterpret_cast<u16 *>(p);
-  }
-  lds.hres = reinterpret_cast<u16 *>(lds.lbest);  // 128 x u16 = the 64 ints of lbest, idle during the seed passes
-  lds.G = a.G;
+  se_carve<LONG>(lds, smem, a);
   lds.smark[lane] = 0; lds.smark[64 + lane] = 0;
   u32 seg_epoch = 0;
 
@@ -604,39 +579,10 @@ hipError_t launch_order_reads_sliced(const DevIndex &ix, const u64 *d_packed, co
 }
 
 // ---- launchers ----------------------------------------------------------------
-u32 se_window_words(u32 max_len, double valid_frac) {
-  const int md = static_cast<i16>(valid_frac * max_len);
-  int bw = 2 * md + 1;
-  if (bw > static_cast<int>(kMaxBand) || bw < 1) bw = kMaxBand;
-  return ((max_len + bw + 15 + 15) >> 4) + 1;
-}
-
-u32 tb_extra_bytes(u32 GW, u32 max_len, double valid_frac) {
-  const int md = static_cast<i16>(valid_frac * max_len);
-  int bw = 2 * md + 1;
-  if (bw > static_cast<int>(kMaxBand) || bw < 0) bw = kMaxBand;
-  if (bw < 1) bw = 1;
-  const size_t need = static_cast<size_t>(max_len + bw) * bw;
-  const size_t have = static_cast<size_t>(kMaxJobs - 1) * GW * 8 + (static_cast<size_t>(8) << kPosCacheBits);
-  return need > have ? static_cast<u32>((need - have + 7) & ~static_cast<size_t>(7)) : 0u;
-}
-
-size_t se_lds_bytes(u32 W, u32 WB, u32 cig_stride, u32 max_len, double valid_frac) {
-  const u32 GW = se_window_words(max_len, valid_frac);
-  const u32 MB = (max_len + kPlaneBlock - 1) / kPlaneBlock;
-  size_t b = static_cast<size_t>(4) * W * 8 + static_cast<size_t>(4) * WB * 8 + static_cast<size_t>(4) * MB * 4 * 8 +
-             (static_cast<size_t>(8) << kPosCacheBits) +
-             static_cast<size_t>(kMaxJobs) * GW * 8 + static_cast<size_t>((cig_stride + 1) & ~1u) * 4 +
-             2 * kSeCap * 4 + 64 * 4 + 2 * 128 * 4 + 64 * 2;
-  b += tb_extra_bytes(GW, max_len, valid_frac);
-  return (b + 15) & ~static_cast<size_t>(15);
-}
-
-int se_resident_waves(u32 W, u32 WB, u32 cig_stride, u32 max_len, double valid_frac) {
+int se_resident_waves(size_t lds) {
   int per_cu = 0, dev = 0;
   hipDeviceProp_t prop;
   if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
-  const size_t lds = se_lds_bytes(W, WB, cig_stride, max_len, valid_frac);
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, map_se_kernel<false, true>, 64, lds) != hipSuccess) return 0;
   // Measured on MI355X at hg38 scale (round 2: scripts/grid_sweep.sh and se_variant.sh, in the history of this repository): what matters is waves without
   // register spills.  10 M reads: one lane per window, 20 waves/CU 1405 ms (28: 1577, 32: 1681); cooperative
@@ -663,17 +609,12 @@ hipError_t launch_pack_reads(const char *d_blob, const u64 *d_off, u64 n, u32 W,
   return hipGetLastError();
 }
 
-size_t se_long_lds_bytes(u32 W, u32 WB, u32 GW) {
-  const size_t b = static_cast<size_t>(4) * W * 8 + static_cast<size_t>(4) * WB * 8 + 2 * kSeCap * 4 + static_cast<size_t>(2) * GW * 8 +
-                   (static_cast<size_t>(8) << kPosCacheBits) + 64 * 4 + 2 * 128 * 4 + 64 * 2;
-  return (b + 15) & ~static_cast<size_t>(15);
-}
 size_t se_long_tb_bytes(u32 max_len) { return (static_cast<size_t>(max_len + kMaxBand) * kMaxBand + 255) & ~static_cast<size_t>(255); }
-int se_long_resident_waves(u32 W, u32 WB, u32 GW) {
+int se_long_resident_waves(size_t lds) {
   int per_cu = 0, dev = 0;
   hipDeviceProp_t prop;
   if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, map_se_long_kernel, 64, se_long_lds_bytes(W, WB, GW)) != hipSuccess) return 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, map_se_long_kernel, 64, lds) != hipSuccess) return 0;
   return min(per_cu, 4) * prop.multiProcessorCount;
 }
 hipError_t launch_collect_long(const u32 *d_lens, u64 n, u32 *d_list, u32 *d_count, hipStream_t st) {
@@ -688,25 +629,21 @@ hipError_t launch_pack_listed(const char *d_blob, const u64 *d_off, const u32 *d
 }
 hipError_t launch_map_se_long(SeArgs a, u32 n_waves, hipStream_t st) {
   if (a.n_reads == 0) return hipSuccess;
-  const size_t lds = se_long_lds_bytes(a.W, a.WB, a.GW);
+  const size_t lds = se_lds_layout<u32>(0, true, lds_shape(a)).bytes;
   const u32 blocks = static_cast<u32>(a.n_reads < n_waves ? a.n_reads : n_waves);
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(map_se_long_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
   hipLaunchKernelGGL(map_se_long_kernel, dim3(blocks), dim3(64), lds, st, a);
   return hipGetLastError();
 }
 
-size_t sam_line_room(u32 GW, u32 tb_extra) {
-  return static_cast<size_t>(kMaxJobs - 1) * GW * 8 + (static_cast<size_t>(8) << kPosCacheBits) + tb_extra;
-}
-
-hipError_t launch_map_se(SeArgs a, u32 max_len, u32 n_waves, bool timed, hipStream_t st) {
+hipError_t launch_map_se(SeArgs a, u32 n_waves, bool timed, hipStream_t st) {
   if (a.n_reads == 0) return hipSuccess;
-  const size_t lds = se_lds_bytes(a.W, a.WB, a.ctmp_cap, max_len, a.size_frac);
+  const size_t lds = se_lds_layout<u32>(0, false, lds_shape(a)).bytes;
   const u32 blocks = static_cast<u32>(a.n_reads < n_waves ? a.n_reads : n_waves);
   const bool bam = a.sam_tail != nullptr && a.sam_format == kRecordsBam;
   if (bam && timed) return hipErrorInvalidValue;  // (no timed build writes BAM pieces: the host leaves such launches without slots)
   // COOP: lanes share a candidate's window on the bit planes (a.G != 0); otherwise one lane per window
-  if (a.G != 0 && a.ix.wrec != nullptr && max_len <= a.ix.wrec_max_len && (a.G == 2 || a.G == 4)) {
+  if (a.G != 0 && a.ix.wrec != nullptr && a.max_len <= a.ix.wrec_max_len && (a.G == 2 || a.G == 4)) {
     if (timed) hipLaunchKernelGGL((map_se_kernel<true, true, true>), dim3(blocks), dim3(64), lds, st, a);
     else if (bam) hipLaunchKernelGGL((map_se_bam_kernel<true, true>), dim3(blocks), dim3(64), lds, st, a);
     else hipLaunchKernelGGL((map_se_kernel<false, true, true>), dim3(blocks), dim3(64), lds, st, a);

@@ -13,7 +13,7 @@ struct SeArgs {
   u64 n_reads;
   u32 W, WB, GW;      // words per packed encoding / 2-letter bit string / genome window
   u32 max_len;        // longest read of the batch
-  u32 tb_extra;       // tb_extra_bytes()
+  u32 tb_extra;       // tb_extra_bytes() (abm_lds_layout.hpp)
   u32 G;              // lanes sharing one candidate window (WaveLds::G)
   int mode;           // ABM_SE_*
   double valid_frac;
@@ -147,32 +147,22 @@ constexpr u8 kRouteSmall = 0, kRouteWhole = 1, kRouteBig = 2;
 // PeArgs::sam_kind: the pair's two records (format_pe), up to two single-end records (format_se: the fallback, or a pair
 // whose ends cannot both be located on one chromosome), or none written -- the host formats the whole pair
 constexpr u8 kPeTextPair = 0, kPeTextSingles = 1, kPeTextHost = 0xFF;
-// LDS a launch of the pair kernels with SAM text takes beyond its usual size: both ends' CigarSink::fin
-constexpr u32 kPeFinBytes = 2 * kSeCap * 4;
-// bytes of the LDS a SAM line is built in (the traceback table's place: window slots 1.., the window cache and the
-// table's extra bytes -- idle once the CIGARs are out), the same in the single-end and the pair kernels; a launch whose
-// text slot (sam_stride) is longer writes no text
-size_t sam_line_room(u32 GW, u32 tb_extra);
-
-// bytes the traceback table needs beyond the LDS it overlays (genome-window slots 1.. and the
-// window cache, both idle while a traceback runs); the kernels carve exactly this much extra
-u32 tb_extra_bytes(u32 GW, u32 max_len, double valid_frac);
-size_t pe_lds_bytes(u32 W, u32 WB, u32 GW, u32 cig_stride, u32 max_len, double valid_frac, u32 cap, bool big);
+// What the kernels' LDS layouts (abm_lds_layout.hpp) are a function of, from an argument block.  A SAM line is built in
+// the layout's table room (lds_table_room; idle once the CIGARs are out), the same in the single-end and the pair
+// kernels; a launch whose text slot (sam_stride) is longer writes no text
+template <class Args> ABM_HD inline LdsShape lds_shape(const Args &a) { return LdsShape{a.W, a.WB, a.GW, a.max_len, a.ctmp_cap, a.tb_extra}; }
 int pe_waves_per_simd(size_t lds, bool timed, bool coop);  // which build of the pair kernels a launch with this much LDS per wave takes
 int pe_text_waves_per_simd();  // ... and the one the launches with SAM text take (launch_map_pe)
 int pe_resident_waves(size_t lds, bool big, int wps);
 hipError_t launch_map_pe(const PeArgs &a, size_t lds, u32 grid, bool big, bool timed, int wps, hipStream_t st, bool text = false);
 hipError_t launch_collect_long_pairs(const u32 *d_lens1, const u32 *d_lens2, u64 n, u32 *d_list, u32 *d_count, hipStream_t st);
-size_t pe_long_lds_bytes(u32 GW);
 size_t pe_long_q_words(u32 W, u32 WB);
-int pe_long_resident_waves(u32 GW);
+int pe_long_resident_waves(size_t lds);
 hipError_t launch_map_pe_long(const PeArgs &a, u32 grid, hipStream_t st);
 // the pairs whose route (PeArgs::need_big) is `want`, heaviest weight class first
 hipError_t launch_collect_big(const u8 *need_big, const u8 *cls, u64 n, u8 want, u32 *class33, u32 *subset, u32 *count,
                               hipStream_t st);
 // the phase-split launches (seed kernel -> hand-over area -> mate kernels; abm_kernels_pe.hip)
-size_t pe_seed_lds_bytes(u32 W, u32 WB, u32 max_len, u32 cap);
-size_t pe_mate_lds_bytes(u32 W, u32 GW, u32 cig_stride, u32 max_len, double valid_frac, u32 cap, bool big);
 int pe_seed_resident_waves(size_t lds, bool coop);
 int pe_mate_resident_waves(size_t lds, bool big);
 hipError_t launch_pe_seed(const PeArgs &a, size_t lds, u32 grid, bool timed, hipStream_t st);
@@ -184,9 +174,10 @@ constexpr u32 kPeTier1Cap = ABM_PE_TIER1_CAP;
 // (a power of two: sort_unique pads a list to the next power of two inside a buffer of this many entries -- builds with
 // 48 and 96 returned wrong pairs, profiles/r03_exp_pe_tier1_cap_small.log; 32 ... 256 measured: 64 and 128 level, 256 slower)
 static_assert(kPeTier1Cap >= 32 && (kPeTier1Cap & (kPeTier1Cap - 1)) == 0, "tier-1 list capacity: a power of two, at least the sets' initial 32");
+// the overlays on fixed-size regions (abm_lds_layout.hpp holds those that need no more than its own constants)
+static_assert(kPeTier1Cap * 4 <= kCacheBytes, "tier 1's scratch table (PeLds::tmp) lies on the window cache");
+static_assert(kSeCap * sizeof(u32) <= kSeCap * sizeof(u32), "the single-end fin (a CIGAR's first kSeCap ops) lies on jpos");
 
-u32 se_window_words(u32 max_len, double valid_frac);
-size_t se_lds_bytes(u32 W, u32 WB, u32 cig_stride, u32 max_len, double valid_frac);
 // seed-extension tables (abm_ext.hip): keys of table `mode` (0: 2-letter, 1 / 2: 3-letter C->T / G->A) with `extra`
 // letters beyond the hashed ones; bytes of scratch a build needs; the build itself (out[ext_keys] entries, n_idx =
 // entries of the table's index array)
@@ -219,14 +210,13 @@ hipError_t launch_order_reads_sliced(const DevIndex &ix, const u64 *d_packed, co
                                      u32 *d_slice_left, u32 *d_order, hipStream_t st);
 inline size_t order_sliced_hist_words(u32 n_slices) { return static_cast<size_t>(n_slices + 1) * 33 + 33 + n_slices + 2; }
 // n_waves = one-wave workgroups of the (persistent) grid
-hipError_t launch_map_se(SeArgs a, u32 max_len, u32 n_waves, bool timed, hipStream_t st);
+hipError_t launch_map_se(SeArgs a, u32 n_waves, bool timed, hipStream_t st);
 // the long-read launch (reads of kLdsReadLen + 1 .. kMaxReadLen bases, listed in a.order, packed by list position)
-size_t se_long_lds_bytes(u32 W, u32 WB, u32 GW);
 size_t se_long_tb_bytes(u32 max_len);
-int se_long_resident_waves(u32 W, u32 WB, u32 GW);
+int se_long_resident_waves(size_t lds);
 hipError_t launch_collect_long(const u32 *d_lens, u64 n, u32 *d_list, u32 *d_count, hipStream_t st);
 hipError_t launch_pack_listed(const char *d_blob, const u64 *d_off, const u32 *d_list, u64 m, u32 W, u64 *d_packed, hipStream_t st);
 hipError_t launch_map_se_long(SeArgs a, u32 n_waves, hipStream_t st);
-int se_resident_waves(u32 W, u32 WB, u32 cig_stride, u32 max_len, double valid_frac);
+int se_resident_waves(size_t lds);
 
 }  // namespace abm

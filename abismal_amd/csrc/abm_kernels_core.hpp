@@ -227,8 +227,28 @@ struct WaveLds {
   u32 G;       // lanes that share one candidate's window (4 or 8), 0 = one lane per window
   u32 max_jobs;  // window slots in gwin: kMaxJobs, or 2 in the long-read kernel (its bands are 61 lanes wide: one slot of lanes)
 };
-constexpr u32 kPosCacheBits = 8;
-constexpr u32 kMaxJobs = 21;  // 64 lanes / narrowest band (3)
+// The single-end kernels' carve: se_lds_layout over this wave's allocation.  LONG: the CIGAR scratch and the traceback
+// table are this wave's pieces of global memory.
+template <bool LONG> __device__ __forceinline__ void se_carve(WaveLds &lds, unsigned char *smem, const SeArgs &a) {
+  const SeLds<unsigned char *> at = se_lds_layout(smem, LONG, lds_shape(a));
+  lds.W = a.W; lds.WB = a.WB; lds.GW = a.GW; lds.G = a.G;
+  lds.MB = LONG ? 0u : lds_mask_blocks(a.max_len);
+  lds.max_jobs = at.slots;
+  lds.qpk = reinterpret_cast<u64 *>(at.qpk);
+  lds.qbits = reinterpret_cast<u64 *>(at.qbits);
+  lds.qmask = reinterpret_cast<u64 *>(at.qmask);
+  lds.ctmp = LONG ? a.long_ctmp + static_cast<u64>(blockIdx.x) * ((a.ctmp_cap + 1) & ~1u) : reinterpret_cast<u32 *>(at.ctmp);
+  lds.jpos = reinterpret_cast<u32 *>(at.jpos);
+  lds.jdf = reinterpret_cast<u32 *>(at.jdf);
+  lds.gwin = reinterpret_cast<u64 *>(at.gwin);
+  lds.pcache = reinterpret_cast<u64 *>(at.pcache);
+  lds.tb = LONG ? a.long_tb + static_cast<u64>(blockIdx.x) * a.long_tb_bytes : at.tb;
+  lds.lbest = reinterpret_cast<int *>(at.lbest);
+  lds.smark = reinterpret_cast<u32 *>(at.smark);
+  lds.sdelta = reinterpret_cast<u32 *>(at.sdelta);
+  lds.mark = reinterpret_cast<u16 *>(at.mark);
+  lds.hres = reinterpret_cast<u16 *>(lds.lbest);  // idle during the seed passes
+}
 
 __device__ __forceinline__ u32 q_nibble(const u64 *qpk, u32 k) {
   return static_cast<u32>(qpk[k >> 4] >> ((k & 15u) << 2)) & 15u;

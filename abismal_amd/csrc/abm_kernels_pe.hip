@@ -66,7 +66,6 @@ struct PairBest {
 // reference's score_t, and the lists are tier 2's (global memory).
 // PHASE: kWhole = seeding and mating in one kernel (tier 2's whole-pair launch, the long-end launch; BIG = false is the
 // unsplit tier 1 of rounds 1-4, kept for same-box comparisons), kSeed / kMate = the two halves of the split
-enum : int { kWhole = 0, kSeed = 1, kMate = 2 };
 #ifndef ABM_PE_RADIX_SORT_MIN
 #define ABM_PE_RADIX_SORT_MIN 512
 #endif
@@ -233,7 +232,7 @@ template <bool BIG, bool COOP, bool LONG = false, int PHASE = kWhole, bool REC =
       // Tier 2's long lists: a radix sort by position, four passes of eight bits between the two per-wave tables in
       // global memory (round 5).  The bitonic network below costs n log2(n)^2 / 128 compare-exchange steps of the wave --
       // 78 passes over a list of 4096 -- where this costs four: per pass a histogram of the digit in LDS (256 counters
-      // in the place of the window slots, idle here), their prefix sums, and a scatter chunk by chunk in which the lanes
+      // at the start of the layout's scratch room, idle here), their prefix sums, and a scatter chunk by chunk in which the lanes
       // of a chunk that share a digit find their rank among themselves from eight ballots.  Equal positions are equal
       // entries (the duplicates unique() drops), so the order among them is of no consequence.
       if (n > kRadixSortMin) {
@@ -304,10 +303,10 @@ template <bool BIG, bool COOP, bool LONG = false, int PHASE = kWhole, bool REC =
     else {
       // tier 2: the buffer is in global memory.  Every pass at distance j < C only pairs elements
       // of the same aligned block of C, so those passes run on a copy of the block in LDS (the
-      // window slots and the window cache are idle here); only distances >= C touch global memory.
+      // layout's scratch room: the window slots and the window cache, idle here); only distances >= C touch global memory.
       u32 *blk = reinterpret_cast<u32 *>(lds.gwin);
       int C = 256;
-      while (2 * C <= static_cast<int>(2 * (lds.max_jobs * lds.GW + (1u << kPosCacheBits))) && 2 * C <= m) C <<= 1;
+      while (2 * C <= static_cast<int>(lds_scratch_words(lds.max_jobs, lds.GW)) && 2 * C <= m) C <<= 1;
       if (C > m) C = m;
       auto local = [&](int k_from, int k_to, int j_top) {  // stages k_from..k_to, distances j_top..1, block by block
         for (int b = 0; b < m; b += C) {
@@ -866,93 +865,12 @@ __global__ __launch_bounds__(64, WPS) void map_pe_kernel(PeArgs a) {
   const int lane = lane_id();
   PeWave<BIG, COOP, LONG, PHASE, REC, TEXT> w{a};
   WaveLds &lds = w.lds;
-  lds.W = a.W; lds.WB = a.WB; lds.GW = a.GW;
-  u32 *after_heap;
-  if constexpr (LONG) {
-    // read data in this wave's piece of global memory; LDS holds the two window slots, the cache and the job lists
-    u64 *q = a.long_q + static_cast<u64>(blockIdx.x) * (8ull * a.W + 8ull * a.WB);
-    lds.qpk = q;
-    lds.qbits = q + 8 * a.W;
-    lds.MB = 0;
-    lds.qmask = nullptr;
-    lds.gwin = reinterpret_cast<u64 *>(smem);
-    lds.max_jobs = 2;
-    lds.pcache = lds.gwin + 2 * a.GW;
-    lds.tb = a.long_tb + static_cast<u64>(blockIdx.x) * a.long_tb_bytes;
-    lds.ctmp = a.long_ctmp + static_cast<u64>(blockIdx.x) * ((a.ctmp_cap + 1) & ~1u);
-    lds.jpos = reinterpret_cast<u32 *>(lds.pcache + (1u << kPosCacheBits));
-  }
-  else if constexpr (PHASE == kSeed) {
-    // (pe_seed_lds_bytes) read data, the window cache, the step's distances, then the set: no alignment state at all
-    lds.qpk = reinterpret_cast<u64 *>(smem);
-    lds.qbits = lds.qpk + 8 * a.W;
-    lds.MB = (a.max_len + kPlaneBlock - 1) / kPlaneBlock;
-    lds.qmask = lds.qbits + 8 * a.WB;  // [2 ends][4][MB][4]
-    lds.pcache = lds.qmask + 8 * lds.MB * 4;
-    lds.gwin = nullptr; lds.max_jobs = 0; lds.tb = nullptr; lds.ctmp = nullptr; lds.jpos = nullptr; lds.jdf = nullptr;
-    w.pl.jidx = nullptr;
-    lds.lbest = reinterpret_cast<int *>(lds.pcache + (1u << kPosCacheBits));
-  }
-  else {
-    lds.qpk = reinterpret_cast<u64 *>(smem);
-    if constexpr (PHASE == kMate) {  // (pe_mate_lds_bytes: the packed encodings are all a mate kernel reads of a read)
-      lds.qbits = nullptr; lds.MB = 0; lds.qmask = nullptr;
-      lds.gwin = lds.qpk + 8 * a.W;
-    }
-    else {
-      lds.qbits = lds.qpk + 8 * a.W;
-      lds.MB = (a.max_len + kPlaneBlock - 1) / kPlaneBlock;
-      lds.qmask = lds.qbits + 8 * a.WB;  // [2 ends][4][MB][4]
-      lds.gwin = lds.qmask + 8 * lds.MB * 4;
-    }
-    lds.max_jobs = kMaxJobs;
-    lds.pcache = lds.gwin + kMaxJobs * a.GW;
-    // the traceback table overlays window slots 1.. and the window cache (a traceback uses slot 0 only)
-    lds.tb = reinterpret_cast<u8 *>(lds.gwin + a.GW);
-    lds.ctmp = reinterpret_cast<u32 *>(reinterpret_cast<u8 *>(lds.pcache + (1u << kPosCacheBits)) + a.tb_extra);
-    lds.jpos = lds.ctmp + a.ctmp_cap;
-  }
-  if constexpr (PHASE != kSeed) {
-    lds.jdf = lds.jpos + kSeCap;
-    w.pl.jidx = lds.jdf + kSeCap;
-    lds.lbest = reinterpret_cast<int *>(w.pl.jidx + kSeCap);
-  }
-  // tier 1: the set's heap is in LDS.  tier 2: a 32768-entry heap per wave would cap the CU at one
-  // wave, so it lives in global memory (L2-resident, touched by this wave only) and occupancy stays normal
-  after_heap = reinterpret_cast<u32 *>(lds.lbest + 64);
-  if (BIG) w.pl.heap = a.heap_ws + static_cast<u64>(blockIdx.x) * a.cap;
-  else { w.pl.heap = after_heap; after_heap += a.cap; }
-  w.pl.cap = a.cap;
-  if (BIG) {
-    u32 *ws = a.list_ws + static_cast<u64>(blockIdx.x) * 4 * a.cap;  // 2 pos arrays + (2 diffs + 2 scores) as i16
-    w.pl.lpos[0] = ws; w.pl.lpos[1] = ws + a.cap;
-    i16 *h = reinterpret_cast<i16 *>(ws + 2 * a.cap);
-    w.pl.ld[0] = h; w.pl.ld[1] = h + a.cap; w.pl.lsc[0] = h + 2 * a.cap; w.pl.lsc[1] = h + 3 * a.cap;
-  }
-  else if constexpr (PHASE == kSeed) {  // one list at a time (positions, diffs)
-    w.pl.lpos[0] = w.pl.lpos[1] = after_heap;
-    i16 *h = reinterpret_cast<i16 *>(after_heap + a.cap);
-    w.pl.ld[0] = w.pl.ld[1] = h; w.pl.lsc[0] = w.pl.lsc[1] = nullptr;
-    after_heap = reinterpret_cast<u32 *>(h + a.cap + (a.cap & 1u));
-  }
-  else {
-    w.pl.lpos[0] = after_heap; w.pl.lpos[1] = after_heap + a.cap;
-    i16 *h = reinterpret_cast<i16 *>(after_heap + 2 * a.cap);
-    w.pl.ld[0] = h; w.pl.ld[1] = h + a.cap; w.pl.lsc[0] = h + 2 * a.cap; w.pl.lsc[1] = h + 3 * a.cap;
-    after_heap = reinterpret_cast<u32 *>(h + 4 * a.cap);
-  }
-  lds.smark = after_heap;
-  lds.sdelta = after_heap + 128;
-  lds.mark = reinterpret_cast<u16 *>(after_heap + 256);
-  lds.hres = reinterpret_cast<u16 *>(lds.lbest);
-  lds.G = a.G;
+  pe_carve<BIG, LONG, PHASE, TEXT>(lds, w.pl, w.fin, w.samp, smem, a);
   if constexpr (PHASE != kMate) { lds.smark[lane] = 0; lds.smark[64 + lane] = 0; }
-  else lds.mark = reinterpret_cast<u16 *>(after_heap);  // (no seed passes: no segment marks)
-  if constexpr (TEXT) w.fin = reinterpret_cast<u32 *>(lds.mark + 64);  // (after the 64 marks: kPeFinBytes more LDS)
   w.seg_epoch = 0;
 
   w.P.heap = w.pl.heap;
-  w.samp = reinterpret_cast<u32 *>(lds.pcache); w.samp_shift = 0; w.samp_n = 0;
+  w.samp_shift = 0; w.samp_n = 0;
   w.P.spill_pos = nullptr; w.P.spill_d = nullptr; w.P.spill_cap = 0; w.P.spilled = false;
   w.stage_pos = nullptr; w.stage_d = nullptr;
   if constexpr (PHASE == kSeed) {
@@ -962,9 +880,6 @@ __global__ __launch_bounds__(64, WPS) void map_pe_kernel(PeArgs a) {
     }
   }
   w.log_base = BIG ? a.log_ws + static_cast<u64>(blockIdx.x) * (32ull + 12ull * a.cap) : nullptr;
-  // scratch table for permuting a list: global for tier 2; tier 1 borrows the window cache (idle outside seed passes)
-  static_assert(kPeTier1Cap * 4 <= (8u << kPosCacheBits), "tier-1 scratch table must fit the window cache");
-  w.pl.tmp = BIG ? a.payload_ws + static_cast<u64>(blockIdx.x) * a.cap : reinterpret_cast<u32 *>(lds.pcache);
   w.P.cap_avail = a.cap;
   w.wt = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   w.n_aln = 0;
@@ -1201,16 +1116,6 @@ __global__ __launch_bounds__(256) void big_scatter_kernel(const u8 *__restrict__
   if (take) subset[base[c] + rank] = static_cast<u32>(r);
 }
 
-size_t pe_lds_bytes(u32 W, u32 WB, u32 GW, u32 cig_stride, u32 max_len, double valid_frac, u32 cap, bool big) {
-  const u32 MB = (max_len + kPlaneBlock - 1) / kPlaneBlock;
-  size_t b = static_cast<size_t>(8) * W * 8 + static_cast<size_t>(8) * WB * 8 + static_cast<size_t>(8) * MB * 4 * 8 +
-             (static_cast<size_t>(8) << kPosCacheBits) + static_cast<size_t>(kMaxJobs) * GW * 8 +
-             static_cast<size_t>(cig_stride) * 4 + 3 * kSeCap * 4 + 64 * 4 + 2 * 128 * 4 + 64 * 2;
-  if (!big) b += static_cast<size_t>(cap) * (4 + 2 * 4 + 4 * 2);
-  b += tb_extra_bytes(GW, max_len, valid_frac);
-  return (b + 15) & ~static_cast<size_t>(15);
-}
-
 int pe_waves_per_simd(size_t lds, bool timed, bool coop) {
   // (LDS of a CU: 160 KB on gfx950)
   return (!timed && coop && lds != 0 && (160u * 1024u) / lds <= 13u) ? 3 : ABM_PE_WAVES_PER_SIMD;
@@ -1256,7 +1161,7 @@ hipError_t launch_map_pe(const PeArgs &a, size_t lds, u32 grid, bool big, bool t
   if (grid == 0) return hipSuccess;
   if (text) {
     // SAM text: the builds on the bit planes (a.G != 0), four waves per SIMD, the planes for ends the window records would
-    // serve as well (the same candidates); lds includes kPeFinBytes
+    // serve as well (the same candidates); lds: the layout with text
     if (timed || a.G == 0) return hipErrorInvalidValue;
     if (a.sam_format == kRecordsBam) {
       if (big) hipLaunchKernelGGL((map_pe_kernel<true, false, true, ABM_PE_WAVES_PER_SIMD, false, kWhole, false, true, true>), dim3(grid), dim3(64), lds, st, a);
@@ -1287,21 +1192,17 @@ hipError_t launch_collect_long_pairs(const u32 *d_lens1, const u32 *d_lens2, u64
   hipLaunchKernelGGL(collect_long_pairs_kernel, dim3(static_cast<u32>((n + 255) / 256)), dim3(256), 0, st, d_lens1, d_lens2, n, d_list, d_count);
   return hipGetLastError();
 }
-size_t pe_long_lds_bytes(u32 GW) {
-  const size_t b = static_cast<size_t>(2) * GW * 8 + (static_cast<size_t>(8) << kPosCacheBits) + 3 * kSeCap * 4 + 64 * 4 + 2 * 128 * 4 + 64 * 2;
-  return (b + 15) & ~static_cast<size_t>(15);
-}
 size_t pe_long_q_words(u32 W, u32 WB) { return 8ull * W + 8ull * WB; }
-int pe_long_resident_waves(u32 GW) {
+int pe_long_resident_waves(size_t lds) {
   int per_cu = 0, dev = 0;
   hipDeviceProp_t prop;
   if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, map_pe_kernel<true, false, false, 1, true>, 64, pe_long_lds_bytes(GW)) != hipSuccess) return 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, map_pe_kernel<true, false, false, 1, true>, 64, lds) != hipSuccess) return 0;
   return std::min(per_cu, 1) * prop.multiProcessorCount;  // (one wave per CU: each has megabytes of workspace in global memory)
 }
 hipError_t launch_map_pe_long(const PeArgs &a, u32 grid, hipStream_t st) {
   if (grid == 0) return hipSuccess;
-  hipLaunchKernelGGL((map_pe_kernel<true, false, false, 1, true>), dim3(grid), dim3(64), pe_long_lds_bytes(a.GW), st, a);
+  hipLaunchKernelGGL((map_pe_kernel<true, false, false, 1, true>), dim3(grid), dim3(64), pe_lds_layout<u32>(0, kWhole, true, true, false, lds_shape(a), a.cap).bytes, st, a);
   return hipGetLastError();
 }
 
@@ -1328,20 +1229,6 @@ hipError_t launch_collect_big(const u8 *need_big, const u8 *cls, u64 n, u8 want,
 #endif
 constexpr int kPeSeedWps = ABM_PE_SEED_WPS, kPeMateWps = ABM_PE_MATE_WPS;
 
-size_t pe_seed_lds_bytes(u32 W, u32 WB, u32 max_len, u32 cap) {
-  const u32 MB = (max_len + kPlaneBlock - 1) / kPlaneBlock;
-  const size_t b = static_cast<size_t>(8) * W * 8 + static_cast<size_t>(8) * WB * 8 + static_cast<size_t>(8) * MB * 4 * 8 +
-                   (static_cast<size_t>(8) << kPosCacheBits) + 64 * 4 + static_cast<size_t>(cap) * 4 /* heap */ +
-                   static_cast<size_t>(cap) * 4 + static_cast<size_t>(cap + (cap & 1u)) * 2 /* one list */ + 2 * 128 * 4 + 64 * 2;
-  return (b + 15) & ~static_cast<size_t>(15);
-}
-size_t pe_mate_lds_bytes(u32 W, u32 GW, u32 cig_stride, u32 max_len, double valid_frac, u32 cap, bool big) {
-  size_t b = static_cast<size_t>(8) * W * 8 + (static_cast<size_t>(8) << kPosCacheBits) + static_cast<size_t>(kMaxJobs) * GW * 8 +
-             static_cast<size_t>(cig_stride) * 4 + 3 * kSeCap * 4 + 64 * 4 + 64 * 2;
-  if (!big) b += static_cast<size_t>(cap) * (4 + 2 * 4 + 4 * 2);
-  b += tb_extra_bytes(GW, max_len, valid_frac);
-  return (b + 15) & ~static_cast<size_t>(15);
-}
 static int resident(const void *fn, size_t lds) {
   int per_cu = 0, dev = 0;
   hipDeviceProp_t prop;
@@ -1375,7 +1262,7 @@ hipError_t launch_pe_seed(const PeArgs &a, size_t lds, u32 grid, bool timed, hip
 }
 hipError_t launch_pe_mate(const PeArgs &a, size_t lds, u32 grid, bool big, bool timed, hipStream_t st, bool text) {
   if (grid == 0) return hipSuccess;
-  if (text) {  // (SAM text: lds includes kPeFinBytes)
+  if (text) {  // (SAM text: lds is the layout with text)
     if (timed) return hipErrorInvalidValue;
     if (a.sam_format == kRecordsBam) {
       if (big) hipLaunchKernelGGL((map_pe_kernel<true, false, false, kPeMateWps, false, kMate, false, true, true>), dim3(grid), dim3(64), lds, st, a);

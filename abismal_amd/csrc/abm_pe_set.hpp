@@ -15,6 +15,61 @@ struct PeLds {
   u32 cap;
 };
 
+// The pair kernels' carve: pe_lds_layout over this wave's allocation.  What a form keeps outside LDS is this wave's piece
+// of a workspace in global memory: the long-end form's read data, traceback table and CIGAR scratch; with BIG the heap
+// (a 32768-entry heap per wave in LDS would cap the CU at one wave; it is L2-resident and touched by this wave only),
+// the lists and the scratch table for permuting a list.  fin: TEXT, both ends' CigarSink::fin; samp: PeWave::samp.
+template <bool BIG, bool LONG, int PHASE, bool TEXT>
+__device__ __forceinline__ void pe_carve(WaveLds &lds, PeLds &pl, u32 *&fin, u32 *&samp, unsigned char *smem, const PeArgs &a) {
+  const PeLdsAt<unsigned char *> at = pe_lds_layout(smem, PHASE, LONG, BIG, TEXT, lds_shape(a), a.cap);
+  lds.W = a.W; lds.WB = a.WB; lds.GW = a.GW; lds.G = a.G;
+  lds.MB = (LONG || PHASE == kMate) ? 0u : lds_mask_blocks(a.max_len);
+  lds.max_jobs = at.slots;
+  if constexpr (LONG) {
+    u64 *q = a.long_q + static_cast<u64>(blockIdx.x) * (8ull * a.W + 8ull * a.WB);
+    lds.qpk = q;
+    lds.qbits = q + 8 * a.W;
+    lds.qmask = nullptr;
+    lds.tb = a.long_tb + static_cast<u64>(blockIdx.x) * a.long_tb_bytes;
+    lds.ctmp = a.long_ctmp + static_cast<u64>(blockIdx.x) * ((a.ctmp_cap + 1) & ~1u);
+  }
+  else {
+    lds.qpk = reinterpret_cast<u64 *>(at.qpk);
+    lds.qbits = reinterpret_cast<u64 *>(at.qbits);
+    lds.qmask = reinterpret_cast<u64 *>(at.qmask);  // [2 ends][4][MB][4]
+    lds.tb = at.tb;
+    lds.ctmp = reinterpret_cast<u32 *>(at.ctmp);
+  }
+  lds.gwin = reinterpret_cast<u64 *>(at.gwin);
+  lds.pcache = reinterpret_cast<u64 *>(at.pcache);
+  lds.jpos = reinterpret_cast<u32 *>(at.jpos);
+  lds.jdf = reinterpret_cast<u32 *>(at.jdf);
+  pl.jidx = reinterpret_cast<u32 *>(at.jidx);
+  lds.lbest = reinterpret_cast<int *>(at.lbest);
+  lds.hres = reinterpret_cast<u16 *>(lds.lbest);
+  pl.cap = a.cap;
+  if (BIG) {
+    pl.heap = a.heap_ws + static_cast<u64>(blockIdx.x) * a.cap;
+    u32 *ws = a.list_ws + static_cast<u64>(blockIdx.x) * 4 * a.cap;  // 2 pos arrays + (2 diffs + 2 scores) as i16
+    pl.lpos[0] = ws; pl.lpos[1] = ws + a.cap;
+    i16 *h = reinterpret_cast<i16 *>(ws + 2 * a.cap);
+    pl.ld[0] = h; pl.ld[1] = h + a.cap; pl.lsc[0] = h + 2 * a.cap; pl.lsc[1] = h + 3 * a.cap;
+    pl.tmp = a.payload_ws + static_cast<u64>(blockIdx.x) * a.cap;
+  }
+  else {
+    pl.heap = reinterpret_cast<u32 *>(at.heap);
+    pl.lpos[0] = reinterpret_cast<u32 *>(at.lpos[0]); pl.lpos[1] = reinterpret_cast<u32 *>(at.lpos[1]);
+    pl.ld[0] = reinterpret_cast<i16 *>(at.ld[0]); pl.ld[1] = reinterpret_cast<i16 *>(at.ld[1]);
+    pl.lsc[0] = reinterpret_cast<i16 *>(at.lsc[0]); pl.lsc[1] = reinterpret_cast<i16 *>(at.lsc[1]);
+    pl.tmp = reinterpret_cast<u32 *>(lds.pcache);  // tier 1 borrows the window cache (idle outside the seed passes)
+  }
+  lds.smark = reinterpret_cast<u32 *>(at.smark);
+  lds.sdelta = reinterpret_cast<u32 *>(at.sdelta);
+  lds.mark = reinterpret_cast<u16 *>(at.mark);
+  fin = reinterpret_cast<u32 *>(at.fin);
+  samp = reinterpret_cast<u32 *>(lds.pcache);
+}
+
 // list element reads (tier 1: LDS; tier 2: this wave's lists in global memory, through L1 -- the
 // binary searches of the mating code revisit the same few lines from every lane)
 template <bool BIG> __device__ __forceinline__ u32 ld_list(const u32 *p) { return *p; }

@@ -111,3 +111,19 @@ def test_product_sim_reproduces_the_fastq_goldens(tmp_path):
             assert hashlib.md5((tmp_path / rel).read_bytes()).hexdigest() == want, rel
             n += 1
     assert n == 7
+
+
+def test_lds_layouts_match_the_frozen_sizes_under_sanitizers(tmp_path):
+    """abm_lds_layout.hpp as plain host C++: every form's bytes against the launchers' former size formulas, regions in order,
+    none overlapping, every overlay inside its room (tests/cpp/lds_layout_check.cpp)."""
+    import shutil
+    import subprocess
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is needed to build the layout check"
+    exe = tmp_path / "lds_layout_check"
+    subprocess.run([gxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", str(exe),
+                    os.path.join(ROOT, "tests", "cpp", "lds_layout_check.cpp")], check=True)
+    r = subprocess.run([str(exe)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert re.search(r"^1808 points, 0 wrong$", r.stdout, re.M), r.stdout
+    assert "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, r.stderr
