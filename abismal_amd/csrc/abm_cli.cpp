@@ -342,6 +342,7 @@ abm_index *open_index(const Options &opt, Chroms &ch) {
   if (abm_index_open(index_path.c_str(), &ix) != 0) die_abm("loading index");
   if (opt.index.empty()) std::remove(index_path.c_str());
   g_min_read_len = 24 + abm_index_window(ix);
+  g_map_read_len = std::max(abm_index_window(ix) + 15u, 29u);  // (DevIndex::map_len)
   for (uint32_t i = 0; i < abm_index_n_chroms(ix); ++i) ch.names.push_back(abm_index_chrom_name(ix, i));
   ch.starts.assign(abm_index_chrom_starts(ix), abm_index_chrom_starts(ix) + ch.names.size() + 1);
   return ix;

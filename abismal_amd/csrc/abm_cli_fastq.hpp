@@ -16,6 +16,7 @@ namespace {
 
 constexpr uint32_t kPadding = 32767;
 uint32_t g_min_read_len = 44;  // key weight + the index's window - 1 (src/abismal.cpp:212-213): 36 with a short-read index
+uint32_t g_map_read_len = 35;  // shortest trimmed read the library maps (DevIndex::map_len, abm_device.hpp): 29 with a short-read index
 
 // ---- FASTQ, with ReadLoader's rules (src/abismal.cpp:164-201) -----------------
 // Stage 1 (one thread per input file) only cuts the file into batches of whole records;
@@ -194,12 +195,12 @@ struct Batch {
 
 // What a read of 44-46 bases finds past its end comes, position by position, from the nearest EARLIER
 // read that is longer than that position -- up to 64 positions out, so a read of kGhostReach = 46 + 64 bases hides
-// everything before it, and reads the reference never preps (shorter than the index's minimum) leave nothing.
+// everything before it, and reads that are not mapped (empty, or shorter than g_map_read_len) leave nothing.
 // ghost_tail: of n records (off[e][k], off[e][k + 1]: read k of end e), scanning backwards, those that are longer in
 // some end than every record after them, until all ends have reached kGhostReach -- the only records of this input
 // that can still be such a source for reads that come later.  Indices in descending order; at most 67 per end.
 constexpr uint32_t kGhostReach = 110;
-inline uint32_t ghost_len(uint64_t len) { return len < g_min_read_len ? 0u : static_cast<uint32_t>(std::min<uint64_t>(len, kGhostReach)); }
+inline uint32_t ghost_len(uint64_t len) { return len < g_map_read_len ? 0u : static_cast<uint32_t>(std::min<uint64_t>(len, kGhostReach)); }
 // (reach: how far each end is covered by the records after these n -- a scan that continues further back in the input
 // passes the same array on; a fresh scan starts from ghost_reach_start)
 inline void ghost_reach_start(uint32_t reach[2], int ends) { reach[0] = 0; reach[1] = ends == 2 ? 0u : kGhostReach; }

@@ -39,7 +39,17 @@ struct DevIndex {
   const u32 *index, *index_t, *index_a;
   u32 max_candidates;
   u32 window;   // seed window of this index: 20, or 12 (--enable-short, src/AbismalIndex.hpp:73-77)
-  u32 min_len;  // shortest read that is mapped: key_weight + window - 1 (src/abismal.cpp:212-213)
+  u32 min_len;  // key_weight + window - 1 (src/abismal.cpp:212-213): what the reference's reader asks of a read's letters
+                // other than N BEFORE it trims, and the shortest alignment that is reported (valid_len, :308-313)
+  // Shortest read that is mapped.  The reader's trimming (:192-194) drops every letter before the first A/C/G/T, so a read
+  // that began with IUPAC letters comes out shorter than min_len and the reference maps it all the same (only an exact
+  // match can be reported for it: choose_se).  Such a read's first max(window, L/2) seed offsets hash 2-letter keys that
+  // reach past its end, as those of a read of min_len .. min_len + 2 bases do (ghost_bits); the kernels follow that down to
+  // the length at which the last of those offsets still has its 16-letter 3-letter key inside the read -- 35 bases with
+  // window 20, 29 with window 12.  Shorter ones (ten and more leading IUPAC letters) are skipped.
+  constexpr u32 map_len() const {
+    return window + kKeyWeight3 - 1 > 2 * kKeyWeight3 - 3 ? window + kKeyWeight3 - 1 : 2 * kKeyWeight3 - 3;
+  }
   // The genome once more for the Hamming filter, as two bit planes: block k = 64 bases = {u64 low bits, u64 high
   // bits} of the base codes (code = index of the base's bit in its one-hot nibble).  A 100-base window is 2-3
   // blocks (32-48 bytes) instead of 64 bytes of nibbles, and the two copies are laid out half a 128-byte line

@@ -199,7 +199,7 @@ __device__ __forceinline__ void map_se_body(const SeArgs &a) {
     u32 *cig_out = a.cig + r * a.cig_stride;
     if (L > kMaxReadLen) too_long = true;
     // (a read beyond this launch's length is the long-read launch's: it overwrites what is stored for it here)
-    if (L >= a.ix.min_len && L <= a.max_len) {
+    if (L >= a.ix.map_len() && L <= a.max_len) {
       // stage the four encodings and derive their 2-letter bit strings
       const u64 *src = a.packed + (LONG ? slot : r) * 4 * a.W;
       for (u32 k = lane; k < 4 * a.W; k += 64) lds.qpk[k] = src[k];
@@ -213,8 +213,8 @@ __device__ __forceinline__ void map_se_body(const SeArgs &a) {
         }
       if constexpr (COOP) build_qmasks(lds, L);
       wave_sync();
-      if (L < max(a.ix.window, L >> 1) + kKeyWeight - 1)  // 44-46 bases: seeds reach past the end of the read
-        ghost_bits(a.packed, a.lens, r, L, a.max_len, a.ix.min_len, a.W, a.WB, lds.qbits);
+      if (L < max(a.ix.window, L >> 1) + kKeyWeight - 1)  // up to 46 bases: seeds reach past the end of the read
+        ghost_bits(a.packed, a.lens, r, L, a.max_len, a.ix.map_len(), a.W, a.WB, lds.qbits);
 
       SeSet S;
       S.begin_read(L);
@@ -242,7 +242,7 @@ __device__ __forceinline__ void map_se_body(const SeArgs &a) {
       if (a.sam_tail != nullptr) {
         // (the line buffer: the traceback table's place -- window slots 1.., the window cache and the table's extra bytes --
         // idle once the CIGAR is out; the host asks for at least sam_stride bytes there: sam_line_room)
-        const u32 len = (L > a.max_len) ? 0xFFFFFFFFu : format_sam_tail<BAM>(a, lds.tb, lds.jpos, r, (L >= a.ix.min_len) ? L : 0u, best, best.pos != 0 ? n_ops : 0u);
+        const u32 len = (L > a.max_len) ? 0xFFFFFFFFu : format_sam_tail<BAM>(a, lds.tb, lds.jpos, r, (L >= a.ix.map_len()) ? L : 0u, best, best.pos != 0 ? n_ops : 0u);
         if (lane == 0) store_out(a.sam_len + r, len);
       }
     }

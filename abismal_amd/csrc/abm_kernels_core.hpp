@@ -838,7 +838,7 @@ __device__ __forceinline__ void locate128(const WaveLds &lds, u32 &seg_epoch, co
 }
 
 // Ghost bits.  The reference hashes a read's first max(20, L/2) seed offsets and extends the last
-// ones while their buckets are too big; for reads of 44-46 bases that reaches PAST the end of the read,
+// ones while their buckets are too big; for reads of up to 46 bases (DevIndex::map_len .. 46) that reaches PAST the end of the read,
 // into whatever the reused per-thread buffer of that encoding still holds: position k carries the
 // nibble the nearest earlier read longer than k left there (prep_read only resizes;
 // src/abismal.cpp:1163-1194, :1302-1308, :1377-1386; zero where nothing was written).
@@ -846,7 +846,7 @@ __device__ __forceinline__ void locate128(const WaveLds &lds, u32 &seg_epoch, co
 // reads handed over before it (lens / packed of the same batch, input order = the reference at -t 1)
 // and writes them into the bit strings qbits (>= 2 words per encoding).  Lane j <-> position L + j.
 __device__ __forceinline__ void ghost_bits(const u64 *__restrict__ packed, const u32 *__restrict__ lens, u64 r, u32 L,
-                                           u32 max_len, u32 min_len, u32 W, u32 WB, u64 *qbits) {
+                                           u32 max_len, u32 map_len, u32 W, u32 WB, u64 *qbits) {
   const int lane = lane_id();
   const u32 k = L + static_cast<u32>(lane);
   bool found = k >= max_len;  // no read of this batch ever wrote that far: still the zero fill
@@ -855,7 +855,7 @@ __device__ __forceinline__ void ghost_bits(const u64 *__restrict__ packed, const
     const u32 len_q = base > static_cast<u64>(lane) ? lens[base - 1 - lane] : 0u;
     for (int t = 0; t < 64; ++t) {
       const u32 lt = rdlane(len_q, t);
-      if (!found && lt >= min_len && lt > k) { found = true; src = base - 1 - t; }
+      if (!found && lt >= map_len && lt > k) { found = true; src = base - 1 - t; }
     }
   }
   const bool have = found && k < max_len && src < r && lens[src] > k;

@@ -125,7 +125,7 @@ template <bool BIG, bool COOP, bool LONG = false, int PHASE = kWhole, bool REC =
       P.spill_pos = stage_pos; P.spill_d = stage_d; P.spill_cap = a.scap; P.spilled = false;
     }
     P.begin_read(len_of(end));
-    if (len_of(end) >= a.ix.min_len) {
+    if (len_of(end) >= a.ix.map_len()) {
       P.cutoff = P.good_cutoff;  // set_specific
       seed_pass<true, TIMED, COOP, REC>(a.ix, w, enc, g_to_a, flags, len_of(end), P, wt, seg_epoch);
       if (!P.overflow && P.wants_sensitive()) {
@@ -665,7 +665,7 @@ template <bool BIG, bool COOP, bool LONG = false, int PHASE = kWhole, bool REC =
   // map_fragments + select_maps + best_single (:1715-1720, :1833-1885)
   template <bool TIMED> __device__ __forceinline__ bool orientation(int O, int endA, bool ar, u64 r, PairBest &best) {
     const int endB = 1 - endA;
-    const bool emptyA = len_of(endA) < a.ix.min_len, emptyB = len_of(endB) < a.ix.min_len;
+    const bool emptyA = len_of(endA) < a.ix.map_len(), emptyB = len_of(endB) < a.ix.map_len();
     if (emptyA && emptyB) {
       // res1/res2 are reset and nothing else happens (:1863-1866)
       return false;
@@ -930,8 +930,8 @@ __global__ __launch_bounds__(64, WPS) void map_pe_kernel(PeArgs a) {
       wave_sync();
       #pragma unroll
       for (int e = 0; e < 2; ++e)  // 44-46 bases: seeds reach past the end of the read (see ghost_bits)
-        if (w.L[e] >= a.ix.min_len && w.L[e] < max(a.ix.window, w.L[e] >> 1) + kKeyWeight - 1)
-          ghost_bits(e ? a.packed2 : a.packed1, e ? a.lens2 : a.lens1, r, w.L[e], a.max_len, a.ix.min_len, a.W, a.WB, lds.qbits + e * 4 * a.WB);
+        if (w.L[e] >= a.ix.map_len() && w.L[e] < max(a.ix.window, w.L[e] >> 1) + kKeyWeight - 1)
+          ghost_bits(e ? a.packed2 : a.packed1, e ? a.lens2 : a.lens1, r, w.L[e], a.max_len, a.ix.map_len(), a.W, a.WB, lds.qbits + e * 4 * a.WB);
     }
 
     if constexpr (PHASE == kSeed) {
@@ -954,9 +954,9 @@ __global__ __launch_bounds__(64, WPS) void map_pe_kernel(PeArgs a) {
 
     PairBest best;
     best.f1 = best.f2 = 0;
-    best.clear(w.L[0] >= a.ix.min_len ? w.L[0] : 0u, w.L[1] >= a.ix.min_len ? w.L[1] : 0u);
-    w.se[0].begin_read(w.L[0] >= a.ix.min_len ? w.L[0] : 0u);
-    w.se[1].begin_read(w.L[1] >= a.ix.min_len ? w.L[1] : 0u);
+    best.clear(w.L[0] >= a.ix.map_len() ? w.L[0] : 0u, w.L[1] >= a.ix.map_len() ? w.L[1] : 0u);
+    w.se[0].begin_read(w.L[0] >= a.ix.map_len() ? w.L[0] : 0u);
+    w.se[1].begin_read(w.L[1] >= a.ix.map_len() ? w.L[1] : 0u);
     w.need_big = false;
     if (BIG && lane < 8) w.log_head(lane)[0] = 0;  // no list logged yet for this pair
     w.max_set = 0;

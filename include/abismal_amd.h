@@ -145,6 +145,11 @@ int abm_ctx_pe_footprint(abm_ctx *ctx, uint64_t n, uint32_t max_len, uint64_t *b
  * map_single_ended / map_single_ended_rand (src/abismal.cpp:1552-1576,
  * :1645-1680): reads are the strings ReadLoader would hand over (already
  * N-trimmed; empty = skipped), concatenated in seq_blob with n+1 offsets.
+ * A trimmed read may be shorter than the reader's minimum of key weight +
+ * window - 1 letters (it began with IUPAC letters, which the reader counts and
+ * then trims, :187-195); the reference maps it all the same, and so does this
+ * library down to 35 bases (29 with a short-read index): below that a read
+ * is left unmapped like an empty one.
  * out_res[i] equals bests[i] and the CIGAR equals r[i].cig just before
  * format_se; CIGAR ops are BAM-encoded (len<<4|op) in out_cig_blob with n+1
  * offsets in out_cig_off (reads without a hit get an empty CIGAR).
