@@ -318,10 +318,15 @@ uint64_t abm_ctx_reads_too_long(abm_ctx *ctx);
 int abm_ctx_filter_on_planes(const abm_ctx *ctx);
 
 /* Measurement hook (no reference counterpart): exact work tallies accumulated by the launches on this context since
- * the previous call, then reset -- of the paired-end kernels always, of the single-end kernel only in its diagnostic
- * build (abm_ctx_set_phase_stamps: the production kernel keeps none, they cost it registers):
- * [0] seed offsets probed, [1] bucket-narrowing search probes, [2] candidates
- * compared, [3] read words compared, [4] candidate-set updates, [5] alignments.
+ * the previous call, then reset:
+ * [0] seed offsets probed, [1] bucket-narrowing search probes (genome letters loaded: a probe that serves both bisections
+ * of a 3-letter step counts once), [2] candidates compared, [3] read words compared (the words fetched per candidate
+ * window: 6 / 8 / 2 per 64-base block on the bit planes by lane group, 6 / 8 on window records, the read's own on the
+ * nibble array), [4] candidate-set updates, [5] alignments scored, [11] candidates served by the position cache (none
+ * on window records), [12] single-end reads whose set held one alignable entry.
+ * The DIAGNOSTIC builds keep them (abm_ctx_set_phase_stamps).  The production builds keep no seed-pass count -- they
+ * cost registers: the single-end kernel returns zeros throughout; the paired-end kernels return zeros in [0]-[3] and
+ * [11] and only what costs them nothing: [4] the updates of the single-end sets alone (best_single), [5] alignments.
  * Feeds the algorithmic-bytes model of SURVEY.md section 8(d). */
 int abm_ctx_take_work(abm_ctx *ctx, uint64_t out[16]);
 /* Diagnostic build of the mapping kernel: adds s_memtime stamps per phase;
@@ -335,7 +340,8 @@ int abm_ctx_set_phase_stamps(abm_ctx *ctx, int enable);
  * buckets' index-entry runs span (the fetched windows' words follow from [2] and [11]).  With phase stamps the paired-end kernel
  * fills [6] probe+narrow, [7] gather+Hamming, [8] replay, [9] single-end
  * fallback, [10] total, [12] sort+unique, [13] pairable-entry alignments,
- * [14] mating + tracebacks, [15] best_single replay. */
+ * [14] mating + tracebacks, [15] best_single replay.  ([10] sums every wave of every launch from its first stamp to its
+ * last, so a tier no pair reached still shows cycles there, and nothing else.) */
 int abm_ctx_take_work_tiers(abm_ctx *ctx, uint64_t out[32]);
 /* Diagnostic build of the single-end kernel only: [0] iterations its scoring rounds ran since the previous call,
  * [1] iterations the same rounds take when each runs to its last row (a round ends early once none of its jobs can
@@ -348,9 +354,10 @@ int abm_ctx_set_read_cycles(abm_ctx *ctx, uint32_t *d_read_cycles);
  * pairable entries, mating + tracebacks, best_single, single-end fallback (NULL = off). */
 int abm_ctx_set_pair_phases(abm_ctx *ctx, uint32_t *d_pair_phases);
 
-/* Measurement hook: when enabled, every mapping-kernel launch is bracketed by
- * HIP events recorded on the stream it is launched on; take_kernel_time waits
- * for them and returns the number of launches and their summed duration. */
+/* Measurement hook: when enabled, every main mapping-kernel launch is bracketed by
+ * HIP events recorded on the stream it is launched on (one per single-end batch, abm_ctx_pe_timed_launches() per
+ * paired-end batch; the extra launches for reads and ends of more than 1024 bases are not bracketed);
+ * take_kernel_time waits for them and returns the number of launches and their summed duration. */
 int abm_ctx_set_timing(abm_ctx *ctx, int enable);
 int abm_ctx_take_kernel_time(abm_ctx *ctx, uint64_t *launches, double *total_ms);
 /* Same, one duration per launch in launch order (paired-end: abm_ctx_pe_timed_launches() per call). */

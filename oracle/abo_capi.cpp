@@ -18,7 +18,7 @@ template <class F> int guarded(F &&f) {
   try { f(); return 0; }
   catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
-constexpr int kWorkValues = 11;
+constexpr int kWorkValues = 12;
 struct MapperBox {
   const Index *ix;
   MapParams par;
@@ -99,8 +99,9 @@ void abo_mapper_free(void *p) { delete static_cast<MapperBox *>(p); }
 // Reads are trimmed ASCII, concatenated in `blob` with n+1 offsets.  Results:
 // out[i] as the reference's bests[i] just before format_se, CIGARs as BAM u32
 // ops in fixed slots of `cig_stride` per read with their count in cig_n[i].
-// work (optional, kWorkValues = 11 values) accumulates the Work tallies: the nine of the
-// algorithmic-bytes model, then the blank-nibble probes of the 2-letter and 3-letter tables.  threads>1 splits the batch
+// work (optional, kWorkValues = 12 values) accumulates the Work tallies: the nine of the
+// algorithmic-bytes model, then the blank-nibble probes of the 2-letter and 3-letter tables and the probes the two
+// bisections of a 3-letter step share.  threads>1 splits the batch
 // into contiguous shards, one Mapper per thread.
 int abo_map_se(void *mapper, int mode, uint64_t n, const char *blob, const uint64_t *off,
                abo_hit *out, uint32_t *cig, uint32_t cig_stride, uint32_t *cig_n,
@@ -138,7 +139,7 @@ int abo_map_se(void *mapper, int mode, uint64_t n, const char *blob, const uint6
   if (work) {
     for (const Work &w : works) {
       const uint64_t v[kWorkValues] = {w.reads, w.seed_iters, w.search_probes, w.candidates, w.words, w.set_updates,
-                                       w.aligns, w.aligns_tb, w.dp_cells, w.blank_probes2, w.blank_probes3};
+                                       w.aligns, w.aligns_tb, w.dp_cells, w.blank_probes2, w.blank_probes3, w.shared_probes3};
       for (int k = 0; k < kWorkValues; ++k) work[k] += v[k];
     }
   }
@@ -197,7 +198,7 @@ int abo_map_pe(void *mapper, int mode, uint64_t n, const char *blob1, const uint
   if (work) {
     for (const Work &w : works) {
       const uint64_t v[kWorkValues] = {w.reads, w.seed_iters, w.search_probes, w.candidates, w.words, w.set_updates,
-                                       w.aligns, w.aligns_tb, w.dp_cells, w.blank_probes2, w.blank_probes3};
+                                       w.aligns, w.aligns_tb, w.dp_cells, w.blank_probes2, w.blank_probes3, w.shared_probes3};
       for (int k = 0; k < kWorkValues; ++k) work[k] += v[k];
     }
   }

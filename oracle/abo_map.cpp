@@ -350,11 +350,13 @@ struct Mapper::Impl {
 
   // std::lower_bound's halving, spelled out (positions need not be sorted
   // beyond kSortDepth letters, so the exact probe sequence matters)
-  template <class Pred> const u32 *first_not(const u32 *lo, const u32 *hi, Pred below) {
+  // (seen / n_seen: the entries probed, in order -- at most 33 for a range of 32-bit size)
+  template <class Pred> const u32 *first_not(const u32 *lo, const u32 *hi, Pred below, const u32 **seen = nullptr, int *n_seen = nullptr) {
     std::ptrdiff_t n = hi - lo;
     while (n > 0) {
       const std::ptrdiff_t half = n >> 1;
       ++work.search_probes;
+      if (seen) seen[(*n_seen)++] = lo + half;
       if (below(lo[half])) { lo += half + 1; n -= half + 1; }
       else n = half;
     }
@@ -391,8 +393,11 @@ struct Mapper::Impl {
     const u32 *plo = lo, *phi = hi;
     for (; p != limit && (hi - lo) > static_cast<std::ptrdiff_t>(par.max_candidates); ++p) {
       plo = lo; phi = hi;
-      const u32 *b1 = first_not(lo, hi, [&](u32 gp) { return sortsym3(probed(g, gp, p, work.blank_probes3), cv) < mid_sym; });
-      const u32 *b2 = first_not(lo, hi, [&](u32 gp) { return sortsym3(probed(g, gp, p, work.blank_probes3), cv) < top_sym; });
+      const u32 *seen1[40], *seen2[40];
+      int k1 = 0, k2 = 0;
+      const u32 *b1 = first_not(lo, hi, [&](u32 gp) { return sortsym3(probed(g, gp, p, work.blank_probes3), cv) < mid_sym; }, seen1, &k1);
+      const u32 *b2 = first_not(lo, hi, [&](u32 gp) { return sortsym3(probed(g, gp, p, work.blank_probes3), cv) < top_sym; }, seen2, &k2);
+      for (int k = 0; k < std::min(k1, k2); ++k) work.shared_probes3 += seen1[k] == seen2[k];
       const u32 sym = sortsym3(q[p], cv);
       if (sym == 0) hi = b1;
       else if (sym == mid_sym) { lo = b1; hi = b2; }

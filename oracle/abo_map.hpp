@@ -58,6 +58,11 @@ struct Work {
   // probes of first_not whose genome letter was a blank nibble (an N the index left unfilled: a long run, the padding),
   // on the 2-letter table and on the 3-letter ones: the tests' proof that a fixture narrows buckets against N runs
   u64 blank_probes2 = 0, blank_probes3 = 0;
+  // 3-letter steps bisect twice over one range (first symbol >= mid, first symbol >= top): the probes of the second
+  // bisection that read the entry the first one read in the same round -- both start at the same midpoint, so at least the
+  // first of every step.  An implementation that runs the two side by side loads that letter once: its probe count is
+  // search_probes - shared_probes3 (what the GPU kernels' diagnostic builds tally)
+  u64 shared_probes3 = 0;
 };
 
 using Cigar = std::vector<u32>;
