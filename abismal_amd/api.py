@@ -1,4 +1,5 @@
 """ctypes binding of include/abismal_amd.h (names and argument meaning as there)."""
+import collections
 import ctypes as C
 import os
 
@@ -23,10 +24,24 @@ EXPORTED_SYMBOLS = [
     "abm_map_se_batch", "abm_map_se_batch_sliced", "abm_ctx_slice_results", "abm_map_se_device", "abm_map_pe_batch", "abm_map_pe_device",
     "abm_max_read_length", "abm_ctx_reads_too_long", "abm_ctx_filter_on_planes", "abm_ctx_long_cigars", "abm_ctx_take_work", "abm_ctx_set_phase_stamps", "abm_ctx_set_read_cycles", "abm_ctx_set_timing", "abm_ctx_take_kernel_time", "abm_ctx_take_kernel_times", "abm_ctx_take_work_tiers", "abm_ctx_take_score_iterations", "abm_stats_allreduce",
     "abm_device_count", "abm_host_alloc", "abm_host_free", "abm_index_set_seed_extension", "abm_index_set_max_candidates", "abm_index_set_direct_narrowing", "abm_ctx_seed_extension", "abm_ctx_rebuild_seed_extension", "abm_device_numa_node",
-    "abm_ctx_set_pe_split", "abm_ctx_pe_split_stats", "abm_ctx_pe_timed_launches", "abm_ctx_set_pair_phases", "abm_device_memory", "abm_ctx_pe_footprint", "abm_index_set_seed_extension_cap", "abm_ctx_pinned_bytes", "abm_ctx_set_sam_tails", "abm_ctx_slice_sam_tails", "abm_ctx_pe_sam_tails", "abm_ctx_set_record_format",
+    "abm_ctx_set_pe_split", "abm_ctx_pe_split_stats", "abm_ctx_pe_timed_launches", "abm_ctx_last_forms", "abm_ctx_set_pair_phases", "abm_device_memory", "abm_ctx_pe_footprint", "abm_index_set_seed_extension_cap", "abm_ctx_pinned_bytes", "abm_ctx_set_sam_tails", "abm_ctx_slice_sam_tails", "abm_ctx_pe_sam_tails", "abm_ctx_set_record_format",
     "abm_index_set_window_records", "abm_ctx_window_records",
     "abm_bgzf_scan", "abm_inflater_create", "abm_inflater_destroy", "abm_inflate_bgzf", "abm_inflate_bgzf_device",
 ]
+
+
+# a build of the mapping kernels by its fields (abm_kernel_form.hpp); phase: "whole", "seed" or "mate"
+SeForm = collections.namedtuple("SeForm", "timed coop rec bam is_long wps")
+PeForm = collections.namedtuple("PeForm", "phase big is_long timed coop rec text bam wps")
+
+
+def decode_form(form_id):
+    """a build's id (abm_ctx_last_forms; its bits: abismal_amd.h) as SeForm or PeForm"""
+    bit = lambda k: bool(form_id >> k & 1)
+    wps = form_id >> 9 & 15
+    if form_id >> 31:
+        return SeForm(bit(0), bit(1), bit(2), bit(3), bit(4), wps)
+    return PeForm(("whole", "seed", "mate")[form_id & 3], bit(2), bit(3), bit(4), bit(5), bit(6), bit(7), bit(8), wps)
 
 
 class AbismalAmdError(RuntimeError):
@@ -524,6 +539,18 @@ class Context:
         self._lib.abm_ctx_pe_timed_launches.argtypes = [C.c_void_p]
         self._lib.abm_ctx_pe_timed_launches.restype = C.c_uint32
         return int(self._lib.abm_ctx_pe_timed_launches(self.handle))
+
+    def last_forms(self, lds=False):
+        """abm_ctx_last_forms: the builds of the mapping kernels the last mapping call launched, in launch order, as SeForm /
+        PeForm; lds=True: (form, LDS bytes per wave of that launch) instead"""
+        u32p = C.POINTER(C.c_uint32)
+        self._lib.abm_ctx_last_forms.argtypes = [C.c_void_p, u32p, u32p, C.c_uint32]
+        self._lib.abm_ctx_last_forms.restype = C.c_uint32
+        n = int(self._lib.abm_ctx_last_forms(self.handle, None, None, 0))
+        ids, size = (C.c_uint32 * max(n, 1))(), (C.c_uint32 * max(n, 1))()
+        n = min(n, int(self._lib.abm_ctx_last_forms(self.handle, ids, size, n)))
+        forms = [decode_form(int(ids[i])) for i in range(n)]
+        return [(f, int(size[i])) for i, f in enumerate(forms)] if lds else forms
 
     def set_pair_phases(self, d_ptr):
         self._lib.abm_ctx_set_pair_phases.argtypes = [C.c_void_p, C.c_void_p]

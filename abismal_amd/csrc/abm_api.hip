@@ -164,6 +164,7 @@ struct abm_ctx {
   int pe_split = -1;     // -1: default (split), 0: tier 1 unsplit, 1: split
   uint32_t pe_scap = 0;  // 0: default
   uint32_t pe_timed_launches = 0;  // HIP-event brackets the last paired-end call recorded (abm_ctx_set_timing)
+  std::vector<std::pair<uint32_t, uint32_t>> last_forms;  // the last mapping call's launches in order: {build's id, LDS bytes per wave} (abm_ctx_last_forms)
   DevBuf<char> blob2;
   DevBuf<abm::u64> off2;
   DevBuf<abm::u32> lens, order, class33;
@@ -204,7 +205,7 @@ struct abm_ctx {
   // every device entry point reuses this context's workspaces: a call first makes its stream wait for
   // the previous call's work (whatever stream that ran on), so consecutive calls never overlap
   hipEvent_t last_done = nullptr;
-  std::map<uint64_t, int> se_waves;
+  std::map<uint64_t, int> se_waves;  // resident waves by (donor form's id, LDS bytes): the occupancy query costs milliseconds
   // staging for the host-buffer entry points
   DevBuf<char> blob;
   DevBuf<abm::u64> off;
@@ -390,6 +391,27 @@ LaunchShape launch_shape(const abm_ctx *ctx, abm::u32 max_len, double valid_frac
   return s;
 }
 
+// What the selectors (abm_kernel_form.hpp) are told about a launch of this context with shape s; text: the launch has
+// slots for records.  The launches that follow ask through these alone, and a build that ran is noted in the context
+bool records_fit(const abm_ctx *ctx, const LaunchShape &s) { return ctx->dix.wrec != nullptr && s.eff_len <= ctx->dix.wrec_max_len; }
+abm::SeChoice se_choice(const abm_ctx *ctx, const LaunchShape &s, abm::SeRole role, bool text) {
+  return abm::se_select(abm::SeFacts{role, s.G, records_fit(ctx, s), ctx->phase_stamps, text, ctx->sam_format == ABM_RECORDS_BAM});
+}
+abm::u32 pe_role_cap(abm::PeRole role) {  // entries of a wave's lists
+  return role == abm::PeRole::kTier1 || role == abm::PeRole::kSeed || role == abm::PeRole::kMateSmall ? abm::kPeTier1Cap : abm::kPeCapLarge;
+}
+abm::PeChoice pe_choice(const abm_ctx *ctx, const LaunchShape &s, abm::PeRole role, bool text) {
+  int wps = 0;  // (experiments: the register budget of tier 1 unsplit / tier 2 forced)
+  if (role == abm::PeRole::kTier1 || role == abm::PeRole::kTier2)
+    if (const char *e = experiment_env(role == abm::PeRole::kTier2 ? "ABM_PE_WPS2" : "ABM_PE_WPS")) { if (e[0] == '3' || e[0] == '4') wps = e[0] - '0'; }
+  const size_t lds = abm::pe_lds_bytes(abm::pe_role_form(role, text), lds_shape_of(s), pe_role_cap(role));
+  return abm::pe_select(abm::PeFacts{role, s.G, records_fit(ctx, s), ctx->phase_stamps, text, ctx->sam_format == ABM_RECORDS_BAM, lds, wps});
+}
+void note_form(abm_ctx *ctx, abm::u32 id, size_t lds) {
+  const std::pair<uint32_t, uint32_t> l{id, static_cast<uint32_t>(lds)};
+  if (ctx->last_forms.empty() || ctx->last_forms.back() != l) ctx->last_forms.push_back(l);  // (a launch in rounds: once)
+}
+
 // a work counter of its own for every launch: a small ring, so launches queued on different streams never share one
 unsigned long long *fresh_counter(abm_ctx *ctx, hipStream_t st) {
   unsigned long long *counter = ctx->next_read.p + (ctx->launch_seq++ & 63u);
@@ -438,7 +460,7 @@ template <class Args> void arena_setup(abm_ctx *ctx, Args &a, bool pinned, hipSt
 // do not; the host then formats every line as before)
 abm::u32 se_text_stride(const abm_ctx *ctx, const LaunchShape &s, abm::u32 cig_stride, bool host_results, bool sliced) {
   if (!ctx->sam_on || !host_results || !sliced) return 0;
-  if (ctx->sam_format == ABM_RECORDS_BAM && ctx->phase_stamps) return 0;  // (the diagnostic builds write no BAM pieces; the pair kernels' write no records at all)
+  if (!se_choice(ctx, s, abm::SeRole::kMain, true).ok) return 0;  // (no build writes these records: the host formats them)
   const abm::u32 stride = ctx->sam_format == ABM_RECORDS_BAM ? bam_stride_for(s.eff_len, cig_stride) : sam_stride_for(ctx, s.eff_len, cig_stride);
   return stride <= abm::lds_table_room(s.GW, s.tb_extra) ? stride : 0;
 }
@@ -476,9 +498,11 @@ void se_long_reads(abm_ctx *ctx, const abm::SeArgs &main, uint64_t n, const char
   HIPCHK(hipStreamSynchronize(st));
   const LaunchShape s = launch_shape(ctx, max_len, valid_frac, ShapeKind::kLong);
   const abm::u32 cap2 = (s.ctmp_cap + 1) & ~1u;
+  const abm::SeForm form = se_choice(ctx, s, abm::SeRole::kLong, false).form;
+  const size_t lds = abm::se_lds_bytes(form, lds_shape_of(s));
   int waves = 0;
   if (count) {
-    waves = abm::se_long_resident_waves(abm::se_lds_layout<abm::u32>(0, true, lds_shape_of(s)).bytes);
+    waves = abm::se_resident_waves(form, lds);
     if (waves <= 0) throw HipFail("map_se_long_kernel does not fit on this device (LDS)");
   }
   const abm::u32 round = 1024;
@@ -507,7 +531,8 @@ void se_long_reads(abm_ctx *ctx, const abm::SeArgs &main, uint64_t n, const char
     a.host_tail = nullptr;
     a.read_cycles = nullptr;
     a.next_read = fresh_counter(ctx, st);
-    HIPCHK(abm::launch_map_se_long(a, grid, st));
+    HIPCHK(abm::launch_se(form, a, lds, grid, st));
+    note_form(ctx, form.id(), lds);
   }
   if (host.host_results) {  // what the main launch's last wave would have published (abm_map_se_batch waits for the stream)
     HIPCHK(hipMemcpyAsync(&ctx->h_tail.p[0], main.cig_arena_count, 4, hipMemcpyDeviceToHost, st));
@@ -524,6 +549,7 @@ void se_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
   if (n == 0) return;
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamWaitEvent(st, ctx->last_done, 0));
+  ctx->last_forms.clear();
   // reads beyond kLdsReadLen bases (rare: long-read libraries) are mapped by a launch of their own afterwards (se_long_reads)
   const bool has_long = max_len > abm::kLdsReadLen;
   const LaunchShape s = launch_shape(ctx, max_len, params->valid_frac, ShapeKind::kSingle);
@@ -585,21 +611,25 @@ void se_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
     a.sam_allow_ambig = ctx->sam_allow_ambig;
     a.sam_format = ctx->sam_format;
   }
-  // the occupancy query costs milliseconds: remember it per launch shape
-  const uint64_t key = (static_cast<uint64_t>(s.W) << 48) ^ (static_cast<uint64_t>(s.eff_len) << 8) ^ static_cast<uint64_t>(s.size_frac * 255.0);
+  const abm::SeChoice build = se_choice(ctx, s, abm::SeRole::kMain, sam_stride != 0);
+  if (!build.ok) throw std::logic_error("no build of map_se_kernel for this launch");
+  const size_t lds = abm::se_lds_bytes(build.form, abm::lds_shape(a));
+  const uint64_t key = (static_cast<uint64_t>(abm::se_donor(build.form).id()) << 32) | lds;
   int waves;
   auto it = ctx->se_waves.find(key);
   if (it != ctx->se_waves.end()) waves = it->second;
-  else { waves = abm::se_resident_waves(abm::se_lds_layout<abm::u32>(0, false, abm::lds_shape(a)).bytes); ctx->se_waves[key] = waves; }
+  else { waves = abm::se_resident_waves(build.form, lds); ctx->se_waves[key] = waves; }
   if (waves <= 0) throw HipFail("map_se_kernel does not fit on this device (LDS/occupancy)");
   abm::u32 grid = static_cast<abm::u32>(waves);  // persistent: one wave per resident slot
   if (const char *e = experiment_env("ABM_GRID_WAVES")) grid = std::max(64, std::atoi(e));
+  grid = static_cast<abm::u32>(std::min<uint64_t>(n, grid));
 
   a.drained = host.signal_drained ? ctx->drained : nullptr;
   timed_launch(ctx, st, [&] {
     a.next_read = fresh_counter(ctx, st);
-    HIPCHK(abm::launch_map_se(a, grid, ctx->phase_stamps, st));
+    HIPCHK(abm::launch_se(build.form, a, lds, grid, st));
   });
+  note_form(ctx, build.form.id(), lds);
   if (has_long) se_long_reads(ctx, a, n, d_blob, d_off, std::min<abm::u32>(max_len, abm::kMaxReadLen), params->valid_frac, host, st);
   HIPCHK(hipEventRecord(ctx->last_done, st));
 }
@@ -706,19 +736,22 @@ void pe_tier2_reserve(abm_ctx *ctx, size_t waves) {
   ctx->log2.reserve(waves * (32 + 12 * cap));
 }
 
-// A launch of the whole-pair kernel (map_pe_kernel) for n pairs: tier 1 unsplit (small sets in LDS) or tier 2 (`large`:
-// sets of kPeCapLarge entries per wave in global memory); text = the launch writes SAM records
-struct PeLaunch { size_t lds; int wps, waves; };
-PeLaunch pe_whole_launch(const abm_ctx *ctx, const LaunchShape &s, uint64_t n, bool large, bool text) {
-  PeLaunch l{};
-  l.lds = abm::pe_lds_layout<abm::u32>(0, abm::kWhole, false, large, text, lds_shape_of(s), large ? abm::kPeCapLarge : abm::kPeTier1Cap).bytes;
-  l.wps = abm::pe_waves_per_simd(l.lds, ctx->phase_stamps, s.G != 0);
-  if (const char *e = experiment_env(large ? "ABM_PE_WPS2" : "ABM_PE_WPS")) { if (!ctx->phase_stamps && s.G != 0 && (e[0] == '3' || e[0] == '4')) l.wps = e[0] - '0'; }
-  if (text) l.wps = abm::pe_text_waves_per_simd();  // (the text builds: launch_map_pe)
-  l.waves = abm::pe_resident_waves(l.lds, large, l.wps);
+// A launch of the pair kernels in one role for n pairs: its build, LDS per wave and resident waves (<= 0: it does not
+// fit); text = the batch's pairs get their records written
+struct PeLaunch {
+  abm::PeForm form;
+  size_t lds;
+  int waves;
+  abm::u32 grid(uint64_t n) const { return waves <= 0 ? 0u : static_cast<abm::u32>(std::min<uint64_t>(n, static_cast<uint64_t>(waves))); }
+};
+PeLaunch pe_launch(const abm_ctx *ctx, const LaunchShape &s, uint64_t n, abm::PeRole role, bool text) {
+  const abm::PeChoice c = pe_choice(ctx, s, role, text);
+  if (!c.ok) throw std::logic_error("no build of map_pe_kernel for this launch");
+  PeLaunch l{c.form, abm::pe_lds_bytes(c.form, lds_shape_of(s), pe_role_cap(role)), 0};
+  l.waves = abm::pe_resident_waves(l.form, l.lds);
   // (tier 2: no more waves than the batch has pairs: every wave owns 2.3 MB of lists, heap and log in global memory -- 7.6 GB
   // for a full grid -- which a batch of a few thousand pairs, or the 32 contexts of two replicas on one device, must not ask for)
-  if (large && l.waves > 0) l.waves = static_cast<int>(std::min<uint64_t>(static_cast<uint64_t>(l.waves), std::max<uint64_t>(n, 64)));
+  if (role == abm::PeRole::kTier2 && l.waves > 0) l.waves = static_cast<int>(std::min<uint64_t>(static_cast<uint64_t>(l.waves), std::max<uint64_t>(n, 64)));
   return l;
 }
 
@@ -741,21 +774,12 @@ size_t pe_hand_entries(const abm_ctx *ctx, uint64_t n) {
   if (const char *e = experiment_env("ABM_PE_HAND_PER_PAIR")) per_pair = static_cast<size_t>(std::max(4, std::atoi(e)));
   return std::min<size_t>(std::max<size_t>(n * per_pair, size_t(1) << 16), 0xFFFFFF00u);
 }
-// the seed kernel's launch: LDS per wave and its grid (0: it does not fit)
-struct PeSeedLaunch { size_t lds; abm::u32 grid; };
-PeSeedLaunch pe_seed_launch(const LaunchShape &s, uint64_t n) {
-  PeSeedLaunch l{};
-  l.lds = abm::pe_lds_layout<abm::u32>(0, abm::kSeed, false, false, false, lds_shape_of(s), abm::kPeTier1Cap).bytes;
-  const int waves = abm::pe_seed_resident_waves(l.lds, s.G != 0);
-  l.grid = waves <= 0 ? 0u : static_cast<abm::u32>(std::min<uint64_t>(n, waves));
-  return l;
-}
-
 // Bytes of one end's SAM-text slot if the launches that finish pairs write both ends' records themselves
 // (abm_ctx_set_sam_tails, format_pe_tails), else 0: their builds on the bit planes only, not the diagnostic ones, and
 // only if a line's slot fits the LDS it is built in; otherwise the batch has no text and the host formats it all
 abm::u32 pe_text_stride(const abm_ctx *ctx, const LaunchShape &s, abm::u32 cig_stride, bool host_results) {
-  if (!ctx->sam_on || !host_results || ctx->phase_stamps || s.G == 0) return 0;
+  if (!ctx->sam_on || !host_results) return 0;
+  if (!pe_choice(ctx, s, abm::PeRole::kTier2, true).ok) return 0;  // (one rule for every launch that finishes pairs, and tier 2 is in every batch)
   const abm::u32 stride = ctx->sam_format == ABM_RECORDS_BAM ? bam_stride_for(s.eff_len, cig_stride) : pe_sam_stride_for(ctx, s.eff_len, cig_stride);
   return stride <= abm::lds_table_room(s.GW, s.tb_extra) ? stride : 0;
 }
@@ -765,8 +789,8 @@ abm::u32 pe_text_stride(const abm_ctx *ctx, const LaunchShape &s, abm::u32 cig_s
 struct PePlan {
   bool split;
   abm::u32 sam_stride, scap;
-  PeLaunch t1;        // tier 1 unsplit (only when !split)
-  PeSeedLaunch seed;  // the seed kernel (only when split)
+  PeLaunch t1;    // tier 1 unsplit (only when !split)
+  PeLaunch seed;  // the seed kernel (only when split)
   PeLaunch t2;
 };
 PePlan pe_plan(const abm_ctx *ctx, uint64_t n, const LaunchShape &s, abm::u32 cig_stride, bool host_results) {
@@ -774,9 +798,9 @@ PePlan pe_plan(const abm_ctx *ctx, uint64_t n, const LaunchShape &s, abm::u32 ci
   p.split = pe_split_on(ctx);
   p.sam_stride = pe_text_stride(ctx, s, cig_stride, host_results);
   p.scap = pe_seed_cap(ctx);
-  if (p.split) p.seed = pe_seed_launch(s, n);
-  else p.t1 = pe_whole_launch(ctx, s, n, false, p.sam_stride != 0);
-  p.t2 = pe_whole_launch(ctx, s, n, true, p.sam_stride != 0);
+  if (p.split) p.seed = pe_launch(ctx, s, n, abm::PeRole::kSeed, false);
+  else p.t1 = pe_launch(ctx, s, n, abm::PeRole::kTier1, p.sam_stride != 0);
+  p.t2 = pe_launch(ctx, s, n, abm::PeRole::kTier2, p.sam_stride != 0);
   return p;
 }
 
@@ -798,7 +822,7 @@ void pe_reserve(abm_ctx *ctx, uint64_t n, const LaunchShape &s, abm::u32 mode_sl
   else {
     // the phase split's hand-over area: list headers per pair, the lists' entries, the bump counter; the seed kernel's
     // per-wave staging area; the second route's pair list
-    const size_t hand_cap = pe_hand_entries(ctx, n), stage = p.scap > abm::kPeTier1Cap ? static_cast<size_t>(p.seed.grid) * p.scap : 0;
+    const size_t hand_cap = pe_hand_entries(ctx, n), stage = p.scap > abm::kPeTier1Cap ? static_cast<size_t>(p.seed.grid(n)) * p.scap : 0;
     ctx->hand_hdr.reserve(n * mode_slots * 2); ctx->hand_count.reserve(1);
     ctx->hand_pos.reserve(hand_cap); ctx->hand_d.reserve(hand_cap);
     ctx->stage_pos.reserve(stage); ctx->stage_d.reserve(stage);
@@ -824,7 +848,8 @@ void pe_long_pairs(abm_ctx *ctx, const abm::PeArgs &main, uint64_t n, const char
   if (count == 0) return;
   const LaunchShape s = launch_shape(ctx, max_len, valid_frac, ShapeKind::kLong);
   const abm::u32 cap2 = (s.ctmp_cap + 1) & ~1u;
-  const int waves = abm::pe_long_resident_waves(abm::pe_lds_layout<abm::u32>(0, abm::kWhole, true, true, false, lds_shape_of(s), abm::kPeCapLarge).bytes);
+  const PeLaunch lng = pe_launch(ctx, s, n, abm::PeRole::kLong, false);
+  const int waves = lng.waves;
   if (waves <= 0) throw HipFail("the paired-end long-end launch does not fit on this device (LDS)");
   const abm::u32 round = 256;  // (a round's packed encodings: 2 x 256 x 4 W words = 32 MB at the longest reads)
   for (abm::u32 at = 0; at < count; at += round) {
@@ -858,7 +883,8 @@ void pe_long_pairs(abm_ctx *ctx, const abm::PeArgs &main, uint64_t n, const char
     a.pair_diag = nullptr;
     a.pair_phases = nullptr;
     a.next_read = fresh_counter(ctx, st);
-    HIPCHK(abm::launch_map_pe_long(a, grid, st));
+    HIPCHK(abm::launch_pe(lng.form, a, lng.lds, grid, st));
+    note_form(ctx, lng.form.id(), lng.lds);
     HIPCHK(hipStreamSynchronize(st));  // (the next round reuses the packed encodings and the count word)
   }
 }
@@ -874,6 +900,7 @@ void pe_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
   if (n >= (1ull << 32)) throw std::invalid_argument("batch too large (>= 2^32 pairs)");
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamWaitEvent(st, ctx->last_done, 0));
+  ctx->last_forms.clear();
   // (ends beyond kLdsReadLen bases: tiers 1 and 2 treat such a pair as empty; pe_long_pairs maps it afterwards)
   const bool has_long = max_len > abm::kLdsReadLen;
   const LaunchShape s = launch_shape(ctx, max_len, params->valid_frac, ShapeKind::kPair);
@@ -925,6 +952,10 @@ void pe_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
   }
   arena_setup(ctx, a, host.host_results, st);
   const size_t events_before = ctx->events_used;
+  auto launch = [&](const PeLaunch &l, abm::u32 grid) {
+    timed_launch(ctx, st, [&] { HIPCHK(abm::launch_pe(l.form, a, l.lds, grid, st)); });
+    note_form(ctx, l.form.id(), l.lds);
+  };
   a.cap = abm::kPeTier1Cap;
   if (!split) {
     // tier 1 unsplit: every pair, seeding and mating in one kernel, small sets in LDS
@@ -933,9 +964,7 @@ void pe_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
     a.payload_ws = ctx->payload1.p;
     a.list_ws = nullptr;
     a.next_read = fresh_counter(ctx, st);
-    timed_launch(ctx, st, [&] {
-      HIPCHK(abm::launch_map_pe(a, t1.lds, static_cast<abm::u32>(std::min<uint64_t>(n, t1.waves)), false, ctx->phase_stamps, t1.wps, st, text));
-    });
+    launch(t1, t1.grid(n));
   }
   else {
     // tier 1 split by phase.  SEED: both seed passes of every orientation call's two ends, shaped like the single-end
@@ -946,24 +975,21 @@ void pe_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
     a.hand_cap = static_cast<abm::u32>(std::min<size_t>(std::min(ctx->hand_pos.cap, ctx->hand_d.cap), 0xFFFFFF00u));
     a.split_stats = ctx->split_stats.p;
     HIPCHK(hipMemsetAsync(ctx->hand_count.p, 0, sizeof(unsigned long long), st));
-    const PeSeedLaunch &seed = p.seed;
-    if (seed.grid == 0) throw HipFail("map_pe_kernel (seed) does not fit on this device");
+    const PeLaunch &seed = p.seed;
+    if (seed.waves <= 0) throw HipFail("map_pe_kernel (seed) does not fit on this device");
     a.scap = p.scap;
     if (a.scap > a.cap) { a.stage_pos = ctx->stage_pos.p; a.stage_d = ctx->stage_d.p; }
     a.payload_ws = nullptr;
     a.list_ws = nullptr;
     a.next_read = fresh_counter(ctx, st);
-    timed_launch(ctx, st, [&] { HIPCHK(abm::launch_pe_seed(a, seed.lds, seed.grid, ctx->phase_stamps, st)); });
+    launch(seed, seed.grid(n));
     // MATE, small lists (every list of the pair within kPeTier1Cap entries: LDS): sort, scoring, mating, tracebacks,
     // best_single, fallback -- instruction-bound, it overlaps with the other contexts' seed kernels
-    const size_t lds_m = abm::pe_lds_layout<abm::u32>(0, abm::kMate, false, false, text, abm::lds_shape(a), a.cap).bytes;
-    const int waves_m = abm::pe_mate_resident_waves(lds_m, false);
-    if (waves_m <= 0) throw HipFail("map_pe_kernel (mate) does not fit on this device");
+    const PeLaunch mate = pe_launch(ctx, s, n, abm::PeRole::kMateSmall, text);
+    if (mate.waves <= 0) throw HipFail("map_pe_kernel (mate) does not fit on this device");
     a.order = nullptr;  // (in input order: the lists were handed over in whatever order the seed kernel finished them)
     a.next_read = fresh_counter(ctx, st);
-    timed_launch(ctx, st, [&] {
-      HIPCHK(abm::launch_pe_mate(a, lds_m, static_cast<abm::u32>(std::min<uint64_t>(n, waves_m)), false, ctx->phase_stamps, st, text));
-    });
+    launch(mate, mate.grid(n));
   }
   // tier 2: lists and heaps of up to 32768 entries per wave in global memory
   {
@@ -978,13 +1004,13 @@ void pe_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
     a.work = ctx->work.p + 16;  // tier 2 tallies separately (abm_ctx_take_work_tiers)
     if (split) {
       // the pairs whose lists outgrew LDS inside the seed kernel's staging area: mated from global memory (nothing is seeded twice)
-      const size_t lds_mb = abm::pe_lds_layout<abm::u32>(0, abm::kMate, false, true, text, abm::lds_shape(a), a.cap).bytes;
-      const int waves_mb = std::min(abm::pe_mate_resident_waves(lds_mb, true), t2.waves);  // (the two launches share the workspaces)
+      const PeLaunch mate_big = pe_launch(ctx, s, n, abm::PeRole::kMateBig, text);
+      const int waves_mb = std::min(mate_big.waves, t2.waves);  // (the two launches share the workspaces)
       if (waves_mb <= 0) throw HipFail("map_pe_kernel (mate, tier 2) does not fit on this device");
       HIPCHK(abm::launch_collect_big(ctx->need_big.p, ctx->cls.p, n, abm::kRouteBig, ctx->class33_b.p, ctx->subset_b.p, ctx->subset_count_b.p, st));
       a.subset = ctx->subset_b.p; a.subset_count = ctx->subset_count_b.p;
       a.next_read = fresh_counter(ctx, st);
-      timed_launch(ctx, st, [&] { HIPCHK(abm::launch_pe_mate(a, lds_mb, static_cast<abm::u32>(waves_mb), true, ctx->phase_stamps, st, text)); });
+      launch(mate_big, static_cast<abm::u32>(waves_mb));
       a.subset = ctx->subset.p; a.subset_count = ctx->subset_count.p;
     }
     // the pairs whose candidate sets outgrew tier 1 (the seed kernel): the whole pair again, one wave each, 32768-entry sets
@@ -995,7 +1021,7 @@ void pe_device(abm_ctx *ctx, int mode, const abm_params *params, uint64_t n, con
       a.finished = ctx->finished.p;
       a.host_tail = ctx->h_tail.p;
     }
-    timed_launch(ctx, st, [&] { HIPCHK(abm::launch_map_pe(a, t2.lds, static_cast<abm::u32>(t2.waves), true, ctx->phase_stamps, t2.wps, st, text)); });
+    launch(t2, static_cast<abm::u32>(t2.waves));
     a.finished = nullptr;
     a.host_tail = nullptr;
   }
@@ -1090,7 +1116,7 @@ int abm_ctx_pe_footprint(abm_ctx *ctx, uint64_t n, uint32_t max_len, uint64_t *b
     HIPCHK(hipSetDevice(ctx->device));
     const uint32_t L = std::min<uint32_t>(std::max<uint32_t>(max_len, 48), abm::kLdsReadLen);
     const uint64_t W = words_for(L);
-    const uint64_t w2 = static_cast<uint64_t>(std::max(pe_whole_launch(ctx, launch_shape(ctx, L, 0.1, ShapeKind::kPair), n, true, false).waves, 0));
+    const uint64_t w2 = static_cast<uint64_t>(std::max(pe_launch(ctx, launch_shape(ctx, L, 0.1, ShapeKind::kPair), n, abm::PeRole::kTier2, false).waves, 0));
     const uint64_t cap = abm::kPeCapLarge;
     uint64_t b = w2 * (cap * 4 + 4 * cap * 4 + cap * 4 + (32 + 12 * cap) * 4);  // payload, lists, heap, log
     b += 2 * n * 4 * W * 8;                   // packed encodings of both ends
@@ -1726,6 +1752,15 @@ int abm_ctx_pe_split_stats(abm_ctx *ctx, uint64_t out[4]) {
 }
 
 uint32_t abm_ctx_pe_timed_launches(const abm_ctx *ctx) { return ctx ? ctx->pe_timed_launches : 0; }
+uint32_t abm_ctx_last_forms(const abm_ctx *ctx, uint32_t *ids, uint32_t *lds_bytes, uint32_t cap) {
+  if (!ctx) return 0;
+  const uint32_t n = static_cast<uint32_t>(ctx->last_forms.size());
+  for (uint32_t i = 0; i < n && i < cap; ++i) {
+    if (ids) ids[i] = ctx->last_forms[i].first;
+    if (lds_bytes) lds_bytes[i] = ctx->last_forms[i].second;
+  }
+  return n;
+}
 
 uint64_t abm_ctx_pinned_bytes(const abm_ctx *c) {
   if (!c) return 0;

@@ -11,6 +11,7 @@
 #include <string>
 
 namespace abm { void set_last_error(const std::string &what); }  // abm_api.hip
+namespace abm { int resident_waves(const void *kernel, size_t lds, int per_cu_cap); }  // abm_kernels.hip: the one occupancy query
 
 namespace {
 
@@ -225,9 +226,9 @@ int abm_inflater_create(int device, abm_inflater **out) {
       inf->device = device;
       hipDeviceProp_t prop;
       HIPCHK(hipGetDeviceProperties(&prop, device));
-      int per_cu = 0;
-      HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, inflate_bgzf_kernel, 64, 0));
-      inf->max_waves = static_cast<u32>(std::max(1, prop.multiProcessorCount)) * static_cast<u32>(std::max(1, per_cu));
+      // (at least one wave per CU, whatever the query answers)
+      const int waves = abm::resident_waves(reinterpret_cast<const void *>(inflate_bgzf_kernel), 0, 1 << 20);
+      inf->max_waves = static_cast<u32>(std::max({1, prop.multiProcessorCount, waves}));
       HIPCHK(hipStreamCreateWithFlags(&inf->stream, hipStreamNonBlocking));
     }
     catch (...) { delete inf; throw; }

@@ -3,12 +3,9 @@
 // into the candidate set -> banded alignment -> CIGAR).  One wavefront maps one
 // read; see DESIGN.md for the data layout and the reasoning.
 #include <type_traits>
+#include <utility>
 #include "abm_kernels_core.hpp"
 #include "abm_sam.hpp"
-
-#ifndef ABM_SE_WAVES_PER_SIMD
-#define ABM_SE_WAVES_PER_SIMD 5  // 96 VGPRs per lane, 20 waves per CU
-#endif
 
 
 namespace abm {
@@ -309,15 +306,15 @@ __device__ __forceinline__ void map_se_body(const SeArgs &a) {
   }
 }
 
-// (the launch bound's second argument is waves per SIMD: 5 x 4 SIMDs = 20 one-wave workgroups per CU)
-// REC: the filter reads the window records (DevIndex::wrec) -- a launch none of whose reads is longer than they serve
-template <bool TIMED, bool COOP, bool REC = false>
-__global__ __launch_bounds__(64, ABM_SE_WAVES_PER_SIMD) void map_se_kernel(SeArgs a) { map_se_body<TIMED, COOP, false, REC>(a); }
-// the untimed builds once more, writing BAM pieces where those write SAM text (a launch with SeArgs::sam_format ==
-// kRecordsBam; builds of their own, so that the ones that existed keep their code: DESIGN.md 4.5)
-template <bool COOP, bool REC>
-__global__ __launch_bounds__(64, ABM_SE_WAVES_PER_SIMD) void map_se_bam_kernel(SeArgs a) { map_se_body<false, COOP, false, REC, true>(a); }
-__global__ __launch_bounds__(64, 1) void map_se_long_kernel(SeArgs a) { map_se_body<false, false, true>(a); }
+// One kernel per row of kSeForms (abm_kernel_form.hpp): F is the row's id.  (The launch bound's second argument is waves
+// per SIMD: 5 x 4 SIMDs = 20 one-wave workgroups per CU.)  The builds that write BAM pieces are builds of their own, so
+// that the ones that write SAM text keep their code
+template <u32 F>
+__global__ __launch_bounds__(64, se_form_of(F).wps) void map_se_kernel(SeArgs a) {
+  constexpr SeForm f = se_form_of(F);
+  static_assert(f.valid(), "no such build of the single-end kernel");
+  map_se_body<f.timed, f.coop, f.is_long, f.rec, f.bam>(a);
+}
 
 // reads of this batch that the long-read launch takes: kLdsReadLen < length <= kMaxReadLen
 __global__ __launch_bounds__(256) void collect_long_kernel(const u32 *__restrict__ lens, u64 n, u32 *__restrict__ list,
@@ -579,17 +576,35 @@ hipError_t launch_order_reads_sliced(const DevIndex &ix, const u64 *d_packed, co
 }
 
 // ---- launchers ----------------------------------------------------------------
-int se_resident_waves(size_t lds) {
+// the one occupancy query: one-wave workgroups of `kernel` with lds bytes each on a CU, at most per_cu_cap, times the CUs
+int resident_waves(const void *kernel, size_t lds, int per_cu_cap) {
   int per_cu = 0, dev = 0;
   hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, map_se_kernel<false, true>, 64, lds) != hipSuccess) return 0;
-  // Measured on MI355X at hg38 scale (round 2: scripts/grid_sweep.sh and se_variant.sh, in the history of this repository): what matters is waves without
-  // register spills.  10 M reads: one lane per window, 20 waves/CU 1405 ms (28: 1577, 32: 1681); cooperative
-  // window loads with 8 rounds in flight, 16 waves at 128 registers 1029 ms (20 waves at 96 with spills:
-  // 1386); with 2 rounds in flight 20 waves fit almost without spills: 923 ms (24 waves: 999).
-  constexpr int kSeWavesPerCu = 4 * ABM_SE_WAVES_PER_SIMD;
-  return min(per_cu, kSeWavesPerCu) * prop.multiProcessorCount;
+  if (kernel == nullptr || hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64, lds) != hipSuccess) return 0;
+  return min(per_cu, per_cu_cap) * prop.multiProcessorCount;
+}
+
+template <size_t... I> static const void *se_kernel_at(int i, std::index_sequence<I...>) {
+  static const void *const fns[] = {reinterpret_cast<const void *>(&map_se_kernel<kSeForms[I].id()>)...};
+  return fns[i];
+}
+const void *se_kernel(SeForm f) {
+  const int i = se_form_index(f);
+  return i < 0 ? nullptr : se_kernel_at(i, std::make_index_sequence<kSeFormCount>{});
+}
+// (the single-end cap of 4 x ABM_SE_WAVES_PER_SIMD waves per CU, se_waves_per_cu_cap: measured on MI355X at hg38 scale
+// -- round 2: scripts/grid_sweep.sh and se_variant.sh, in the history of this repository -- what matters is waves without
+// register spills.  10 M reads: one lane per window, 20 waves/CU 1405 ms (28: 1577, 32: 1681); cooperative window loads
+// with 8 rounds in flight, 16 waves at 128 registers 1029 ms (20 waves at 96 with spills: 1386); with 2 rounds in flight
+// 20 waves fit almost without spills: 923 ms (24 waves: 999).)
+hipError_t launch_se(SeForm f, const SeArgs &a, size_t lds, u32 grid, hipStream_t st) {
+  if (grid == 0) return hipSuccess;
+  const void *fn = se_kernel(f);
+  if (fn == nullptr) return hipErrorInvalidValue;
+  if (f.is_long) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+  void *args[] = {const_cast<SeArgs *>(&a)};
+  return hipLaunchKernel(fn, dim3(grid), dim3(64), args, lds, st);
 }
 
 hipError_t launch_make_planes(const u64 *d_genome, u64 n_words, u64 n_bases, u64 n_blocks, u64 *d_planes0,
@@ -610,13 +625,6 @@ hipError_t launch_pack_reads(const char *d_blob, const u64 *d_off, u64 n, u32 W,
 }
 
 size_t se_long_tb_bytes(u32 max_len) { return (static_cast<size_t>(max_len + kMaxBand) * kMaxBand + 255) & ~static_cast<size_t>(255); }
-int se_long_resident_waves(size_t lds) {
-  int per_cu = 0, dev = 0;
-  hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, map_se_long_kernel, 64, lds) != hipSuccess) return 0;
-  return min(per_cu, 4) * prop.multiProcessorCount;
-}
 hipError_t launch_collect_long(const u32 *d_lens, u64 n, u32 *d_list, u32 *d_count, hipStream_t st) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(collect_long_kernel, dim3(static_cast<u32>((n + 255) / 256)), dim3(256), 0, st, d_lens, n, d_list, d_count);
@@ -627,38 +635,4 @@ hipError_t launch_pack_listed(const char *d_blob, const u64 *d_off, const u32 *d
   hipLaunchKernelGGL(pack_listed_kernel, dim3(static_cast<u32>((m * W + 255) / 256)), dim3(256), 0, st, d_blob, d_off, d_list, m, W, d_packed);
   return hipGetLastError();
 }
-hipError_t launch_map_se_long(SeArgs a, u32 n_waves, hipStream_t st) {
-  if (a.n_reads == 0) return hipSuccess;
-  const size_t lds = se_lds_layout<u32>(0, true, lds_shape(a)).bytes;
-  const u32 blocks = static_cast<u32>(a.n_reads < n_waves ? a.n_reads : n_waves);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(map_se_long_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-  hipLaunchKernelGGL(map_se_long_kernel, dim3(blocks), dim3(64), lds, st, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_map_se(SeArgs a, u32 n_waves, bool timed, hipStream_t st) {
-  if (a.n_reads == 0) return hipSuccess;
-  const size_t lds = se_lds_layout<u32>(0, false, lds_shape(a)).bytes;
-  const u32 blocks = static_cast<u32>(a.n_reads < n_waves ? a.n_reads : n_waves);
-  const bool bam = a.sam_tail != nullptr && a.sam_format == kRecordsBam;
-  if (bam && timed) return hipErrorInvalidValue;  // (no timed build writes BAM pieces: the host leaves such launches without slots)
-  // COOP: lanes share a candidate's window on the bit planes (a.G != 0); otherwise one lane per window
-  if (a.G != 0 && a.ix.wrec != nullptr && a.max_len <= a.ix.wrec_max_len && (a.G == 2 || a.G == 4)) {
-    if (timed) hipLaunchKernelGGL((map_se_kernel<true, true, true>), dim3(blocks), dim3(64), lds, st, a);
-    else if (bam) hipLaunchKernelGGL((map_se_bam_kernel<true, true>), dim3(blocks), dim3(64), lds, st, a);
-    else hipLaunchKernelGGL((map_se_kernel<false, true, true>), dim3(blocks), dim3(64), lds, st, a);
-  }
-  else if (a.G != 0) {
-    if (timed) hipLaunchKernelGGL((map_se_kernel<true, true>), dim3(blocks), dim3(64), lds, st, a);
-    else if (bam) hipLaunchKernelGGL((map_se_bam_kernel<true, false>), dim3(blocks), dim3(64), lds, st, a);
-    else hipLaunchKernelGGL((map_se_kernel<false, true>), dim3(blocks), dim3(64), lds, st, a);
-  }
-  else {
-    if (timed) hipLaunchKernelGGL((map_se_kernel<true, false>), dim3(blocks), dim3(64), lds, st, a);
-    else if (bam) hipLaunchKernelGGL((map_se_bam_kernel<false, false>), dim3(blocks), dim3(64), lds, st, a);
-    else hipLaunchKernelGGL((map_se_kernel<false, false>), dim3(blocks), dim3(64), lds, st, a);
-  }
-  return hipGetLastError();
-}
-
 }  // namespace abm

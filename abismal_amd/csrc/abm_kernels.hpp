@@ -2,6 +2,7 @@
 // abm_kernels.hip).
 #pragma once
 #include "abm_device.hpp"
+#include "abm_kernel_form.hpp"
 
 namespace abm {
 
@@ -151,22 +152,20 @@ constexpr u8 kPeTextPair = 0, kPeTextSingles = 1, kPeTextHost = 0xFF;
 // the layout's table room (lds_table_room; idle once the CIGARs are out), the same in the single-end and the pair
 // kernels; a launch whose text slot (sam_stride) is longer writes no text
 template <class Args> ABM_HD inline LdsShape lds_shape(const Args &a) { return LdsShape{a.W, a.WB, a.GW, a.max_len, a.ctmp_cap, a.tb_extra}; }
-int pe_waves_per_simd(size_t lds, bool timed, bool coop);  // which build of the pair kernels a launch with this much LDS per wave takes
-int pe_text_waves_per_simd();  // ... and the one the launches with SAM text take (launch_map_pe)
-int pe_resident_waves(size_t lds, bool big, int wps);
-hipError_t launch_map_pe(const PeArgs &a, size_t lds, u32 grid, bool big, bool timed, int wps, hipStream_t st, bool text = false);
+// A form's kernel (nullptr: no such build), one-wave workgroups of it that are resident at once -- by its donor's
+// occupancy (abm_kernel_form.hpp), 0: it does not fit -- and its launch: `grid` one-wave workgroups with lds bytes each
+const void *pe_kernel(PeForm f);
+const void *se_kernel(SeForm f);
+int resident_waves(const void *kernel, size_t lds, int per_cu_cap);
+inline int pe_resident_waves(PeForm f, size_t lds) { return resident_waves(pe_kernel(pe_donor(f)), lds, pe_waves_per_cu_cap(f)); }
+inline int se_resident_waves(SeForm f, size_t lds) { return resident_waves(se_kernel(se_donor(f)), lds, se_waves_per_cu_cap(f)); }
+hipError_t launch_pe(PeForm f, const PeArgs &a, size_t lds, u32 grid, hipStream_t st);
+hipError_t launch_se(SeForm f, const SeArgs &a, size_t lds, u32 grid, hipStream_t st);
 hipError_t launch_collect_long_pairs(const u32 *d_lens1, const u32 *d_lens2, u64 n, u32 *d_list, u32 *d_count, hipStream_t st);
 size_t pe_long_q_words(u32 W, u32 WB);
-int pe_long_resident_waves(size_t lds);
-hipError_t launch_map_pe_long(const PeArgs &a, u32 grid, hipStream_t st);
 // the pairs whose route (PeArgs::need_big) is `want`, heaviest weight class first
 hipError_t launch_collect_big(const u8 *need_big, const u8 *cls, u64 n, u8 want, u32 *class33, u32 *subset, u32 *count,
                               hipStream_t st);
-// the phase-split launches (seed kernel -> hand-over area -> mate kernels; abm_kernels_pe.hip)
-int pe_seed_resident_waves(size_t lds, bool coop);
-int pe_mate_resident_waves(size_t lds, bool big);
-hipError_t launch_pe_seed(const PeArgs &a, size_t lds, u32 grid, bool timed, hipStream_t st);
-hipError_t launch_pe_mate(const PeArgs &a, size_t lds, u32 grid, bool big, bool timed, hipStream_t st, bool text = false);
 #ifndef ABM_PE_TIER1_CAP
 #define ABM_PE_TIER1_CAP 128
 #endif
@@ -209,14 +208,9 @@ hipError_t launch_order_reads_sliced(const DevIndex &ix, const u64 *d_packed, co
                                      u8 *d_cls, const u32 *d_slice_first, u32 n_slices, u16 *d_slice_id, u32 *d_hist,
                                      u32 *d_slice_left, u32 *d_order, hipStream_t st);
 inline size_t order_sliced_hist_words(u32 n_slices) { return static_cast<size_t>(n_slices + 1) * 33 + 33 + n_slices + 2; }
-// n_waves = one-wave workgroups of the (persistent) grid
-hipError_t launch_map_se(SeArgs a, u32 n_waves, bool timed, hipStream_t st);
 // the long-read launch (reads of kLdsReadLen + 1 .. kMaxReadLen bases, listed in a.order, packed by list position)
 size_t se_long_tb_bytes(u32 max_len);
-int se_long_resident_waves(size_t lds);
 hipError_t launch_collect_long(const u32 *d_lens, u64 n, u32 *d_list, u32 *d_count, hipStream_t st);
 hipError_t launch_pack_listed(const char *d_blob, const u64 *d_off, const u32 *d_list, u64 m, u32 W, u64 *d_packed, hipStream_t st);
-hipError_t launch_map_se_long(SeArgs a, u32 n_waves, hipStream_t st);
-int se_resident_waves(size_t lds);
 
 }  // namespace abm

@@ -14,6 +14,7 @@
 // sensitive pass) go through the WHOLE-pair kernel: the same code unsplit, one
 // wave per pair with 32768-entry sets in global memory (tier 2).
 #include <climits>
+#include <utility>
 #include "abm_kernels_core.hpp"
 #include "abm_pe_set.hpp"
 #include "abm_sam.hpp"
@@ -21,10 +22,7 @@
 // Waves per SIMD the pair kernels are compiled for: 4 (128 registers per lane), and for the production kernels on the
 // bit planes also 3 (170 registers): with 2x150-base pairs the LDS of a wave allows 13 waves per CU anyway, and the
 // build with more registers is the faster one there; with 2x100 the LDS allows 16 and four waves per SIMD win
-// (profiles/r03_exp_pe_loop_and_registers.log, r03_exp_pe_2x100_variants.log).  pe_waves_per_simd() picks per launch.
-#ifndef ABM_PE_WAVES_PER_SIMD
-#define ABM_PE_WAVES_PER_SIMD 4
-#endif
+// (profiles/r03_exp_pe_loop_and_registers.log, r03_exp_pe_2x100_variants.log).  pe_select() (abm_kernel_form.hpp) picks per launch.
 
 namespace abm {
 
@@ -853,14 +851,13 @@ __device__ __forceinline__ void format_pe_tails(const PeArgs &a, u8 *line, const
 // REC: the seed passes filter on the window records (DevIndex::wrec) -- a launch none of whose ends is longer than they serve
 // TEXT: the pair's SAM records are written as well (PeArgs::sam_tail, format_pe_tails)
 // BAM: ... as BAM pieces (TEXT builds of their own, so that the ones that existed keep their code)
-template <bool BIG, bool TIMED, bool COOP, int WPS, bool LONG = false, int PHASE = kWhole, bool REC = false, bool TEXT = false, bool BAM = false>
-__global__ __launch_bounds__(64, WPS) void map_pe_kernel(PeArgs a) {
-  static_assert(!BAM || TEXT, "BAM pieces: a build with the pair's records");
-  static_assert(!REC || (COOP && PHASE != kMate), "window records feed the cooperative filter of the seed passes");
-  static_assert(!LONG || (BIG && !COOP && !TIMED && PHASE == kWhole), "the long-end launch: tier 2's lists, nibble filter, no stamps");
-  static_assert(PHASE != kSeed || !BIG, "the seed kernel keeps its lists in LDS (and its staging area)");
-  static_assert(PHASE != kMate || !COOP, "the mate kernels fetch no candidate windows");
-  static_assert(!TEXT || (!LONG && !TIMED && PHASE != kSeed), "SAM text: the launches that finish pairs in LDS");
+// One kernel per row of kPeForms (abm_kernel_form.hpp): F is the row's id, PeForm::valid what the fields may be together
+template <u32 F>
+__global__ __launch_bounds__(64, pe_form_of(F).wps) void map_pe_kernel(PeArgs a) {
+  constexpr PeForm form = pe_form_of(F);
+  static_assert(form.valid(), "no such build of the pair kernels");
+  constexpr bool BIG = form.big, TIMED = form.timed, COOP = form.coop, LONG = form.is_long, REC = form.rec, TEXT = form.text, BAM = form.bam;
+  constexpr int PHASE = form.phase;
   extern __shared__ __align__(16) unsigned char smem[];
   const int lane = lane_id();
   PeWave<BIG, COOP, LONG, PHASE, REC, TEXT> w{a};
@@ -1116,66 +1113,20 @@ __global__ __launch_bounds__(256) void big_scatter_kernel(const u8 *__restrict__
   if (take) subset[base[c] + rank] = static_cast<u32>(r);
 }
 
-int pe_waves_per_simd(size_t lds, bool timed, bool coop) {
-  // (LDS of a CU: 160 KB on gfx950)
-  return (!timed && coop && lds != 0 && (160u * 1024u) / lds <= 13u) ? 3 : ABM_PE_WAVES_PER_SIMD;
+template <size_t... I> static const void *pe_kernel_at(int i, std::index_sequence<I...>) {
+  static const void *const fns[] = {reinterpret_cast<const void *>(&map_pe_kernel<kPeForms[I].id()>)...};
+  return fns[i];
 }
-
-int pe_text_waves_per_simd() { return ABM_PE_WAVES_PER_SIMD; }
-
-int pe_resident_waves(size_t lds, bool big, int wps) {
-  int per_cu = 0, dev = 0;
-  hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
-  hipError_t e;
-  if (wps == 3) e = big ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, map_pe_kernel<true, false, true, 3>, 64, lds)
-                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, map_pe_kernel<false, false, true, 3>, 64, lds);
-  else e = big ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, map_pe_kernel<true, false, true, ABM_PE_WAVES_PER_SIMD>, 64, lds)
-               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, map_pe_kernel<false, false, true, ABM_PE_WAVES_PER_SIMD>, 64, lds);
-  if (e != hipSuccess) return 0;
-  return per_cu * prop.multiProcessorCount;
+const void *pe_kernel(PeForm f) {
+  const int i = pe_form_index(f);
+  return i < 0 ? nullptr : pe_kernel_at(i, std::make_index_sequence<kPeFormCount>{});
 }
-
-static bool pe_records(const PeArgs &a) { return a.G == 4 && a.ix.wrec != nullptr && a.max_len <= a.ix.wrec_max_len; }
-template <bool BIG, bool TIMED>
-static void launch_pe_variant(const PeArgs &a, size_t lds, u32 grid, int wps, hipStream_t st) {
-  // a.G != 0: the filter reads the genome's bit planes (cooperative window loads) -- or, for ends the window records serve, those
-  if (BIG && pe_records(a)) {
-    if constexpr (BIG) {
-      if constexpr (!TIMED) {
-        if (wps == 3) { hipLaunchKernelGGL((map_pe_kernel<true, false, true, 3, false, kWhole, true>), dim3(grid), dim3(64), lds, st, a); return; }
-      }
-      hipLaunchKernelGGL((map_pe_kernel<true, TIMED, true, ABM_PE_WAVES_PER_SIMD, false, kWhole, true>), dim3(grid), dim3(64), lds, st, a);
-    }
-  }
-  else if (a.G != 0) {
-    if constexpr (!TIMED) {
-      if (wps == 3) { hipLaunchKernelGGL((map_pe_kernel<BIG, false, true, 3>), dim3(grid), dim3(64), lds, st, a); return; }
-    }
-    hipLaunchKernelGGL((map_pe_kernel<BIG, TIMED, true, ABM_PE_WAVES_PER_SIMD>), dim3(grid), dim3(64), lds, st, a);
-  }
-  else hipLaunchKernelGGL((map_pe_kernel<BIG, TIMED, false, ABM_PE_WAVES_PER_SIMD>), dim3(grid), dim3(64), lds, st, a);
-}
-
-hipError_t launch_map_pe(const PeArgs &a, size_t lds, u32 grid, bool big, bool timed, int wps, hipStream_t st, bool text) {
+hipError_t launch_pe(PeForm f, const PeArgs &a, size_t lds, u32 grid, hipStream_t st) {
   if (grid == 0) return hipSuccess;
-  if (text) {
-    // SAM text: the builds on the bit planes (a.G != 0), four waves per SIMD, the planes for ends the window records would
-    // serve as well (the same candidates); lds: the layout with text
-    if (timed || a.G == 0) return hipErrorInvalidValue;
-    if (a.sam_format == kRecordsBam) {
-      if (big) hipLaunchKernelGGL((map_pe_kernel<true, false, true, ABM_PE_WAVES_PER_SIMD, false, kWhole, false, true, true>), dim3(grid), dim3(64), lds, st, a);
-      else hipLaunchKernelGGL((map_pe_kernel<false, false, true, ABM_PE_WAVES_PER_SIMD, false, kWhole, false, true, true>), dim3(grid), dim3(64), lds, st, a);
-    }
-    else if (big) hipLaunchKernelGGL((map_pe_kernel<true, false, true, ABM_PE_WAVES_PER_SIMD, false, kWhole, false, true>), dim3(grid), dim3(64), lds, st, a);
-    else hipLaunchKernelGGL((map_pe_kernel<false, false, true, ABM_PE_WAVES_PER_SIMD, false, kWhole, false, true>), dim3(grid), dim3(64), lds, st, a);
-    return hipGetLastError();
-  }
-  if (big && timed) launch_pe_variant<true, true>(a, lds, grid, wps, st);
-  else if (big) launch_pe_variant<true, false>(a, lds, grid, wps, st);
-  else if (timed) launch_pe_variant<false, true>(a, lds, grid, wps, st);
-  else launch_pe_variant<false, false>(a, lds, grid, wps, st);
-  return hipGetLastError();
+  const void *fn = pe_kernel(f);
+  if (fn == nullptr) return hipErrorInvalidValue;
+  void *args[] = {const_cast<PeArgs *>(&a)};
+  return hipLaunchKernel(fn, dim3(grid), dim3(64), args, lds, st);
 }
 
 // ---- the long-end launch --------------------------------------------------------------------------------------
@@ -1193,18 +1144,6 @@ hipError_t launch_collect_long_pairs(const u32 *d_lens1, const u32 *d_lens2, u64
   return hipGetLastError();
 }
 size_t pe_long_q_words(u32 W, u32 WB) { return 8ull * W + 8ull * WB; }
-int pe_long_resident_waves(size_t lds) {
-  int per_cu = 0, dev = 0;
-  hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, map_pe_kernel<true, false, false, 1, true>, 64, lds) != hipSuccess) return 0;
-  return std::min(per_cu, 1) * prop.multiProcessorCount;  // (one wave per CU: each has megabytes of workspace in global memory)
-}
-hipError_t launch_map_pe_long(const PeArgs &a, u32 grid, hipStream_t st) {
-  if (grid == 0) return hipSuccess;
-  hipLaunchKernelGGL((map_pe_kernel<true, false, false, 1, true>), dim3(grid), dim3(64), pe_lds_layout<u32>(0, kWhole, true, true, false, lds_shape(a), a.cap).bytes, st, a);
-  return hipGetLastError();
-}
 
 hipError_t launch_collect_big(const u8 *need_big, const u8 *cls, u64 n, u8 want, u32 *class33, u32 *subset, u32 *count,
                               hipStream_t st) {
@@ -1215,71 +1154,6 @@ hipError_t launch_collect_big(const u8 *need_big, const u8 *cls, u64 n, u8 want,
   hipLaunchKernelGGL(big_hist_kernel, dim3(blocks), dim3(256), 0, st, need_big, cls, n, want, class33);
   hipLaunchKernelGGL(big_bases_kernel, dim3(1), dim3(64), 0, st, class33, count);
   hipLaunchKernelGGL(big_scatter_kernel, dim3(blocks), dim3(256), 0, st, need_big, cls, n, want, class33, subset);
-  return hipGetLastError();
-}
-
-// ---- the phase-split launches ------------------------------------------------------------------------------------
-// Registers: the seed kernel is built for kPeSeedWps waves per SIMD, the mate kernels for kPeMateWps (what each needs
-// without scratch: profiles/r05_pe_split_resources.log)
-#ifndef ABM_PE_SEED_WPS
-#define ABM_PE_SEED_WPS 4
-#endif
-#ifndef ABM_PE_MATE_WPS
-#define ABM_PE_MATE_WPS 4
-#endif
-constexpr int kPeSeedWps = ABM_PE_SEED_WPS, kPeMateWps = ABM_PE_MATE_WPS;
-
-static int resident(const void *fn, size_t lds) {
-  int per_cu = 0, dev = 0;
-  hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, lds) != hipSuccess) return 0;
-  return per_cu * prop.multiProcessorCount;
-}
-int pe_seed_resident_waves(size_t lds, bool coop) {
-  return coop ? resident(reinterpret_cast<const void *>(map_pe_kernel<false, false, true, kPeSeedWps, false, kSeed>), lds)
-              : resident(reinterpret_cast<const void *>(map_pe_kernel<false, false, false, kPeSeedWps, false, kSeed>), lds);
-}
-int pe_mate_resident_waves(size_t lds, bool big) {
-  return big ? resident(reinterpret_cast<const void *>(map_pe_kernel<true, false, false, kPeMateWps, false, kMate>), lds)
-             : resident(reinterpret_cast<const void *>(map_pe_kernel<false, false, false, kPeMateWps, false, kMate>), lds);
-}
-hipError_t launch_pe_seed(const PeArgs &a, size_t lds, u32 grid, bool timed, hipStream_t st) {
-  if (grid == 0) return hipSuccess;
-  if (pe_records(a)) {
-    if (timed) hipLaunchKernelGGL((map_pe_kernel<false, true, true, kPeSeedWps, false, kSeed, true>), dim3(grid), dim3(64), lds, st, a);
-    else hipLaunchKernelGGL((map_pe_kernel<false, false, true, kPeSeedWps, false, kSeed, true>), dim3(grid), dim3(64), lds, st, a);
-  }
-  else if (a.G != 0) {
-    if (timed) hipLaunchKernelGGL((map_pe_kernel<false, true, true, kPeSeedWps, false, kSeed>), dim3(grid), dim3(64), lds, st, a);
-    else hipLaunchKernelGGL((map_pe_kernel<false, false, true, kPeSeedWps, false, kSeed>), dim3(grid), dim3(64), lds, st, a);
-  }
-  else {
-    if (timed) hipLaunchKernelGGL((map_pe_kernel<false, true, false, kPeSeedWps, false, kSeed>), dim3(grid), dim3(64), lds, st, a);
-    else hipLaunchKernelGGL((map_pe_kernel<false, false, false, kPeSeedWps, false, kSeed>), dim3(grid), dim3(64), lds, st, a);
-  }
-  return hipGetLastError();
-}
-hipError_t launch_pe_mate(const PeArgs &a, size_t lds, u32 grid, bool big, bool timed, hipStream_t st, bool text) {
-  if (grid == 0) return hipSuccess;
-  if (text) {  // (SAM text: lds is the layout with text)
-    if (timed) return hipErrorInvalidValue;
-    if (a.sam_format == kRecordsBam) {
-      if (big) hipLaunchKernelGGL((map_pe_kernel<true, false, false, kPeMateWps, false, kMate, false, true, true>), dim3(grid), dim3(64), lds, st, a);
-      else hipLaunchKernelGGL((map_pe_kernel<false, false, false, kPeMateWps, false, kMate, false, true, true>), dim3(grid), dim3(64), lds, st, a);
-    }
-    else if (big) hipLaunchKernelGGL((map_pe_kernel<true, false, false, kPeMateWps, false, kMate, false, true>), dim3(grid), dim3(64), lds, st, a);
-    else hipLaunchKernelGGL((map_pe_kernel<false, false, false, kPeMateWps, false, kMate, false, true>), dim3(grid), dim3(64), lds, st, a);
-    return hipGetLastError();
-  }
-  if (big) {
-    if (timed) hipLaunchKernelGGL((map_pe_kernel<true, true, false, kPeMateWps, false, kMate>), dim3(grid), dim3(64), lds, st, a);
-    else hipLaunchKernelGGL((map_pe_kernel<true, false, false, kPeMateWps, false, kMate>), dim3(grid), dim3(64), lds, st, a);
-  }
-  else {
-    if (timed) hipLaunchKernelGGL((map_pe_kernel<false, true, false, kPeMateWps, false, kMate>), dim3(grid), dim3(64), lds, st, a);
-    else hipLaunchKernelGGL((map_pe_kernel<false, false, false, kPeMateWps, false, kMate>), dim3(grid), dim3(64), lds, st, a);
-  }
   return hipGetLastError();
 }
 

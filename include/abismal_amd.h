@@ -290,6 +290,12 @@ int abm_ctx_pe_split_stats(abm_ctx *ctx, uint64_t out[4]);
 /* HIP-event brackets (abm_ctx_set_timing) the context's last paired-end call recorded, in launch order: split -- seed,
  * mate (LDS lists), mate (lists in device memory), whole pairs = 4; unsplit -- tier 1, tier 2 = 2. */
 uint32_t abm_ctx_pe_timed_launches(const abm_ctx *ctx);
+/* Test hook: which builds of the mapping kernels the context's last mapping call launched, in launch order (a launch
+ * in rounds counts once).  Returns their number and writes the first `cap` of them: each build's id to `ids`, the LDS
+ * bytes a wave of that launch took to `lds_bytes` (either may be null).  An id packs the build's fields.  Bit 31 set,
+ * single-end: bit 0 timed, 1 coop, 2 rec, 3 bam, 4 is_long, bits 9-12 waves per SIMD.  Bit 31 clear, pairs: bits 0-1
+ * phase (0 whole, 1 seed, 2 mate), bit 2 big, 3 is_long, 4 timed, 5 coop, 6 rec, 7 text, 8 bam, bits 9-12 waves per SIMD. */
+uint32_t abm_ctx_last_forms(const abm_ctx *ctx, uint32_t *ids, uint32_t *lds_bytes, uint32_t cap);
 /* page-locked host memory the context holds for results on their way out (its pinned staging buffers, SAM text
  * included), bytes */
 uint64_t abm_ctx_pinned_bytes(const abm_ctx *ctx);

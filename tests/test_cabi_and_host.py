@@ -127,3 +127,20 @@ def test_lds_layouts_match_the_frozen_sizes_under_sanitizers(tmp_path):
     assert r.returncode == 0, r.stdout + r.stderr
     assert re.search(r"^1808 points, 0 wrong$", r.stdout, re.M), r.stdout
     assert "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, r.stderr
+
+
+def test_kernel_forms_match_the_frozen_launch_rules_under_sanitizers(tmp_path):
+    """abm_kernel_form.hpp as plain host C++: the selected build, or the refusal, for every combination of the selectors'
+    inputs against a frozen restatement of the launchers they replaced; every selected form in its table, no dead build,
+    every form's donor the former stand-in (tests/cpp/kernel_form_check.cpp)."""
+    import shutil
+    import subprocess
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is needed to build the form check"
+    exe = tmp_path / "kernel_form_check"
+    subprocess.run([gxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", str(exe),
+                    os.path.join(ROOT, "tests", "cpp", "kernel_form_check.cpp")], check=True)
+    r = subprocess.run([str(exe)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert re.search(r"^18560 points, 0 wrong$", r.stdout, re.M), r.stdout
+    assert "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, r.stderr

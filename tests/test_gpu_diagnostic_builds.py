@@ -1,34 +1,36 @@
 """The diagnostic builds of the mapping kernels (abm_ctx_set_phase_stamps): their results, their work tallies, their cycle
 stamps and the launch timers -- everything bench.py's roofline counts, phase shares and read-by-read comparison rest on.
 
-Diagnostic instantiations, as the launchers select them (TIMED = true), the case that runs each and what proves it ran.
+Diagnostic builds (timed = true), as se_select / pe_select (abm_kernel_form.hpp) choose them, by the fields that tell them
+apart, the case that runs each and what proves it ran.  (tests/test_gpu_kernel_forms.py asserts the builds themselves, as
+the context reports them; the proofs here are the tallies' own.)
 Every case maps its batch with the stamps off and on on one context, compares the two runs byte for byte and both with
 the oracle (same_bytes, compare_se / compare_pe), and asserts that the tallies carry cycles (`phase_cycles` total for single-end,
 `cyc_total` of the tier for pairs).
 
-launch_map_se (abm_kernels.hip) -- three:
-  map_se_kernel<true, true, true>   record-fed      test_se_results[rep-records-*, unique-records-*]: window_records() != 0,
+SeForm, timed, not is_long -- three:
+  coop, rec                         record-fed      test_se_results[rep-records-*, unique-records-*]: window_records() != 0,
                                                     window_cache_hits == 0 (this build alone has no position cache)
-  map_se_kernel<true, true>         bit planes      test_se_results[rep-planes-*, unique-planes-*]: filter_on_planes(),
+  coop, no rec                      bit planes      test_se_results[rep-planes-*, unique-planes-*]: filter_on_planes(),
                                                     window_records() == 0, window_cache_hits > 0 on rep
-  map_se_kernel<true, false>        nibble array    test_se_results[iupac-*]: filter_on_planes() == 0; and
+  no coop                           nibble array    test_se_results[iupac-*]: filter_on_planes() == 0; and
                                                     test_read_words_per_window[460] (reads beyond 448 bases)
-launch_map_pe -> launch_pe_variant<BIG, true> (abm_kernels_pe.hip) -- five.  (Tier 1 has TWO filter forms, not three:
-launch_pe_variant takes the record-fed build for BIG only, so an index with records runs tier 1 unsplit on the planes.)
-  <false, true, true, W>            tier 1, planes  test_pe_results[rep-planes-unsplit-*, rep-records-unsplit-*]: no pair routed,
+PeForm, timed, phase whole -- five.  (Tier 1, not big, has TWO filter forms, not three: pe_select takes the record-fed
+build for big and for the seed kernel only, so an index with records runs tier 1 unsplit on the planes.)
+  not big, coop                     tier 1, planes  test_pe_results[rep-planes-unsplit-*, rep-records-unsplit-*]: no pair routed,
                                                     tier 1's cyc_total and seed_offsets > 0
-  <false, true, false, W>           tier 1, nibbles test_pe_results[iupac-unsplit-*]: the same, filter_on_planes() == 0
-  <true, true, true, W, .., REC>    tier 2, records test_pe_results[rep-records-*]: tier 2's seed_offsets > 0 (only the
+  not big, no coop                  tier 1, nibbles test_pe_results[iupac-unsplit-*]: the same, filter_on_planes() == 0
+  big, coop, rec                    tier 2, records test_pe_results[rep-records-*]: tier 2's seed_offsets > 0 (only the
                                                     whole-pair kernel seeds in tier 2), window_records() == 172
-  <true, true, true, W>             tier 2, planes  test_pe_results[rep-planes-*]: tier 2's seed_offsets > 0
-  <true, true, false, W>            tier 2, nibbles test_pe_results[iupac-*]: tier 2's seed_offsets > 0
-launch_pe_seed -- three (kSeed; the split forms):
-  <false, true, true, S, kSeed, REC>  records       test_pe_results[rep-records-split*]: routes add up to the batch
-  <false, true, true, S, kSeed>       planes        test_pe_results[rep-planes-split*]: the same
-  <false, true, false, S, kSeed>      nibbles       test_pe_results[iupac-split*]: the same
-launch_pe_mate -- two (kMate; neither filters, so one build serves every index):
-  <false, true, false, M, kMate>    small lists     test_pe_results[*-split*]: mated_from_lds > 0, tier 1's alignments > 0
-  <true, true, false, M, kMate>     lists in memory test_pe_results[*-split_stage_16384-*]: mated_from_device_memory > 0 and
+  big, coop, no rec                 tier 2, planes  test_pe_results[rep-planes-*]: tier 2's seed_offsets > 0
+  big, no coop                      tier 2, nibbles test_pe_results[iupac-*]: tier 2's seed_offsets > 0
+PeForm, timed, phase seed -- three (the split routes):
+  coop, rec                         records         test_pe_results[rep-records-split*]: routes add up to the batch
+  coop, no rec                      planes          test_pe_results[rep-planes-split*]: the same
+  no coop                           nibbles         test_pe_results[iupac-split*]: the same
+PeForm, timed, phase mate -- two (neither filters, so one build serves every index):
+  not big                           small lists     test_pe_results[*-split*]: mated_from_lds > 0, tier 1's alignments > 0
+  big                               lists in memory test_pe_results[*-split_stage_16384-*]: mated_from_device_memory > 0 and
                                                     tier 2's alignments > 0
 Modes: single-end 0, 1 and 2 and paired 0, 1 and 2 each occur at least twice in the parameter lists below.
 
@@ -742,7 +744,7 @@ def test_pe_per_pair_arrays(beds, bed_name, form):
 # ---- 4. launch timers ------------------------------------------------------------------------------------------------------
 def test_launch_timers(beds):
     """abm_ctx_set_timing: one bracket per single-end batch -- the batch's main launch; the launches se_long_reads adds for
-    reads beyond 1024 bases (launch_map_se_long, one per 1024 such reads) are NOT inside timed_launch, so a batch with such a
+    reads beyond 1024 bases (the is_long build, one launch per 1024 such reads) are NOT inside timed_launch, so a batch with such a
     read still records one, as abismal_amd.h says -- and pe_timed_launches() per paired batch: 2 unsplit (tier 1, tier 2),
     4 split (seed, mate, mate on lists in device memory, whole pairs)"""
     import torch

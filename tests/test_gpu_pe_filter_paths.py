@@ -1,7 +1,7 @@
 """GPU parity of the paired-end path across every Hamming filter its launches choose from, and every end length that
 switches between them.  abm_map_pe_device (abm_api.hip) takes the batch's longest end, at most 1,024 bases, as eff_len
 and sets G = 4 for eff_len <= 192, 8 for eff_len <= 448, 0 beyond that or when the genome has no bit planes (IUPAC
-letters); pe_records() / launch_pe_variant() (abm_kernels_pe.hip) then pick
+letters); pe_select() (abm_kernel_form.hpp) then picks
 
     G == 4 and window records that serve eff_len (108 / 140 / 172)   the record-fed seed kernel (REC)
     G == 4 otherwise                                                 bit planes, four-lane groups
