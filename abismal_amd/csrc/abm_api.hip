@@ -296,7 +296,7 @@ void build_wrec(DeviceReplica &rep, const abm_index &ix) {
   if (const char *e = experiment_env("ABM_WINDOW_RECORDS")) want = std::atoi(e);
   if (want <= 0 || rep.dix.planes[0] == nullptr) return;
   const abm::HostIndex &h = ix.h;
-  const abm::u32 blocks = abm::window_record_blocks_for(static_cast<abm::u32>(std::min(want, 172)));  // (groups of four lanes: reads up to 192 bases)
+  const abm::u32 blocks = abm::window_record_blocks_for(static_cast<abm::u32>(std::min(want, static_cast<int>(abm::kRecordMaxLen))));  // (groups of four lanes: reads up to 192 bases)
   const uint64_t n_idx[3] = {h.index.size(), h.index_t.size(), h.index_a.size()};
   const uint64_t n_entries = n_idx[0] + n_idx[1] + n_idx[2];
   if (n_entries == 0 || (n_entries + 2) * blocks >= 0xFFFFFF00ull) return;

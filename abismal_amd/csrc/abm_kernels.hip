@@ -149,6 +149,7 @@ __device__ __forceinline__ void map_se_body(const SeArgs &a) {
   se_carve<LONG>(lds, smem, a);
   lds.smark[lane] = 0; lds.smark[64 + lane] = 0;
   u32 seg_epoch = 0;
+  u32 memo_n = 0;  // offsets in the bounds memo of the (strand, alphabet) call under way (seed_pass)
 
   // (rc, a_rich) calls per mode, in the reference's order
   // T-rich :1556-1572 | A-rich (-A/-P) | random PBAT :1649-1676
@@ -221,11 +222,11 @@ __device__ __forceinline__ void map_se_body(const SeArgs &a) {
         const u32 enc = (rc ? 2u : 0u) + (g_to_a ? 1u : 0u);
         const u32 flags = (rc ? kFlagRC : 0u) | (ar ? kFlagARich : 0u);
         S.cutoff = S.good_cutoff;  // set_specific
-        seed_pass<true, TIMED, COOP, REC>(a.ix, lds, enc, g_to_a, flags, L, S, wt, seg_epoch);
+        seed_pass<true, TIMED, COOP, REC>(a.ix, lds, enc, g_to_a, flags, L, S, wt, seg_epoch, memo_n);
         // should_do_sensitive, :367-370
         if (S.sz != static_cast<int>(kSeCap) || S.cutoff > S.good_cutoff) {
           S.cutoff = S.top_d();  // set_sensitive
-          seed_pass<false, TIMED, COOP, REC>(a.ix, lds, enc, g_to_a, flags, L, S, wt, seg_epoch);
+          seed_pass<false, TIMED, COOP, REC>(a.ix, lds, enc, g_to_a, flags, L, S, wt, seg_epoch, memo_n);
         }
       }
       ABM_STAMP(t_a);

@@ -2,6 +2,7 @@
 // paired-end mapping kernels (gfx950, one wavefront per read / pair).
 #pragma once
 #include "abm_kernels.hpp"
+#include "abm_seed_bounds.hpp"
 
 namespace abm {
 
@@ -914,9 +915,19 @@ __device__ __forceinline__ long long phase_stamp() {
 // set, and to ask whether an N is within reach of the window (the planes' distance never exceeds the true one -- a blank
 // nibble matches nothing, the planes' code 0 there may match -- so a candidate beyond the cutoff on the planes is beyond
 // it on the nibble array too).  No position cache either: a repeated window costs a third of a line, not a line.
+//
+// The bounds memo (REC, single-end): the sensitive pass looks the first max(window, L/2) offsets up again, with the keys the
+// specific pass of the same call has just used on the same lanes, and of a base bucket it needs only the exact range, or that
+// it holds more than max_candidates (abm_seed_bounds.hpp).  The specific pass knows one or the other before it narrows
+// anything -- from the table entry, or from the counters where it had to load them -- and leaves it in the idle cache
+// region (16 bytes per offset; abm_lds_layout.hpp); the sensitive pass then loads no counter for those offsets.
+// memo_n: offsets recorded by this call's specific pass (uniform; owned by the kernel like seg_epoch).
+#ifndef ABM_SE_BOUNDS_MEMO
+#define ABM_SE_BOUNDS_MEMO true  // (false: the sensitive pass loads every offset's counters, for same-box comparisons)
+#endif
 template <bool SPECIFIC, bool TIMED, bool COOP, bool REC, class Set>
 __device__ __forceinline__ void seed_pass(const DevIndex &ix, const WaveLds &lds, u32 enc, bool g_to_a,
-                                          u32 flags, u32 L, Set &S, WorkTally &wt, u32 &seg_epoch) {
+                                          u32 flags, u32 L, Set &S, WorkTally &wt, u32 &seg_epoch, u32 &memo_n) {
   const int lane = lane_id();
   const u64 *qpk = lds.qpk + enc * lds.W;
   const u64 *qb = lds.qbits + enc * lds.WB;
@@ -932,6 +943,12 @@ __device__ __forceinline__ void seed_pass(const DevIndex &ix, const WaveLds &lds
                        L - n_off + 1 >= max(kKeyWeight + ix.e2, kKeyWeight3 + ix.e3);
   static_assert(!REC || COOP, "window records are filtered cooperatively");
   const u32 rec3 = g_to_a ? ix.wrec_a0 : ix.wrec_t0;  // (REC) record number of the 3-letter table's first entry
+  constexpr bool kMemo = REC && !Set::kAppend && ABM_SE_BOUNDS_MEMO;
+  if constexpr (kMemo) {
+    if (SPECIFIC) memo_n = 0;
+    else wave_sync();  // (the specific pass's memo, written by other lanes' stores as far as the compiler knows)
+  }
+  const bool memo_fits = kMemo && n_off <= kBoundsMemoSlots;  // (SPECIFIC; uniform)
 
   // work tallies: the diagnostic builds keep them, the production kernels do not (they cost the single-end kernel
   // registers: 100 -> 64 bytes per lane of scratch without them; the pair kernels kept them until round 5, when five
@@ -951,22 +968,30 @@ __device__ __forceinline__ void seed_pass(const DevIndex &ix, const WaveLds &lds
     u32 lo2 = 0, hi2 = 0, lo3 = 0, hi3 = 0;
     bool chk2 = false, chk3 = false;
     if (live) {
-      // 25-bit 2-letter key, MSB first (get_1bit_hash, src/AbismalIndex.hpp:285-294)
-      const u32 wq = i >> 6, sq = i & 63u;
-      u64 bits = qb[wq] >> sq;
-      if (sq) bits |= qb[wq + 1] << (64 - sq);
-      const u32 k2 = __brev(static_cast<u32>(bits) & 0x1FFFFFFu) >> 7;
-      // 16-digit base-3 key (get_base_3_hash, src/AbismalIndex.hpp:296-305)
-      const u64 win = q_window16(qpk, lds.W, i, L);
-      u32 k3 = 0;
+      // (sensitive pass: an offset the specific pass of this call recorded needs neither keys nor counters)
+      const bool memo_hit = kMemo && !SPECIFIC && i < memo_n;
+      u64 bits = 0;
+      u32 k2 = 0, k3 = 0;
+      if (!memo_hit) {
+        // 25-bit 2-letter key, MSB first (get_1bit_hash, src/AbismalIndex.hpp:285-294)
+        const u32 wq = i >> 6, sq = i & 63u;
+        bits = qb[wq] >> sq;
+        if (sq) bits |= qb[wq + 1] << (64 - sq);
+        k2 = __brev(static_cast<u32>(bits) & 0x1FFFFFFu) >> 7;
+        // 16-digit base-3 key (get_base_3_hash, src/AbismalIndex.hpp:296-305)
+        const u64 win = q_window16(qpk, lds.W, i, L);
 #pragma unroll
-      for (u32 j = 0; j < 16; ++j)
-        k3 = k3 * 3u + trit(static_cast<u32>(win >> (j << 2)) & 15u, g_to_a);
-      // (keeping the specific pass's counters in LDS for the sensitive pass, which looks the first max(window, L/2)
-      // offsets up again, took 4.4 % of the line requests away and made the kernel 1.6 % slower: measured, removed)
-      // (likewise keeping the specific pass's distances, one byte per candidate, so that the sensitive pass fetches no
-      // window for a bucket entry it has seen: 290 of 2,850 candidates per read found there, -7 % lines, and 2.3 KB more LDS
-      // per wave cost 15 % of the time -- profiles/r02_exp_distance_memo.log)
+        for (u32 j = 0; j < 16; ++j)
+          k3 = k3 * 3u + trit(static_cast<u32>(win >> (j << 2)) & 15u, g_to_a);
+      }
+      // (the bounds memo, measured on the record-fed kernel, 10 M x 100 bp: 1,710 -> 1,487 lines requested per read, -13 %,
+      // and 432 -> 423 ms per launch, three alternating runs each of 440.7-443.9 and 433.2-435.6 ms per step --
+      // profiles/se_bounds_memo_bench_ab.log.  The same idea with the counters in LDS of its own, when the repeated lines
+      // were 4.4 % of a read's, had made the kernel of that time 1.6 % slower.)
+      // (keeping the specific pass's distances too, one byte per candidate, so that the sensitive pass fetches no window for
+      // a bucket entry it has seen: 290 of 2,850 candidates per read found there, -7 % lines, and 2.3 KB more LDS per wave
+      // cost 15 % of the time -- profiles/r02_exp_distance_memo.log.  Not measured again on the idle cache region, where
+      // it would cost no LDS.)
       if (SPECIFIC) {
         u32 probes = 0;
         u32 len2 = kKeyWeight, len3 = kKeyWeight3;
@@ -985,10 +1010,20 @@ __device__ __forceinline__ void seed_pass(const DevIndex &ix, const WaveLds &lds
           lo3 = x3.x; hi3 = x3.x + (x3.y & 0x7FFFFFFu); len3 = kKeyWeight3 + ((x3.y >> 27) & 7u); run3 = st3 != 0;
           if (st2 == 2) { lo2 = ix.counter[k2]; hi2 = ix.counter[k2 + 1]; len2 = kKeyWeight; }  // (not tabulated)
           if (st3 == 2) { lo3 = cnt3[k3]; hi3 = cnt3[k3 + 1]; len3 = kKeyWeight3; }
+          if constexpr (kMemo) if (memo_fits) {
+            const BucketFact f2 = st2 == 2 ? BucketFact{lo2, hi2 - lo2} : bucket_fact_from_table(x2.x, x2.y);
+            const BucketFact f3 = st3 == 2 ? BucketFact{lo3, hi3 - lo3} : bucket_fact_from_table(x3.x, x3.y);
+            lds.pcache[2 * i] = f2.lo | (static_cast<u64>(f2.d) << 32);
+            lds.pcache[2 * i + 1] = f3.lo | (static_cast<u64>(f3.d) << 32);
+          }
         }
         else {
           lo2 = ix.counter[k2]; hi2 = ix.counter[k2 + 1];
           lo3 = cnt3[k3];       hi3 = cnt3[k3 + 1];
+          if constexpr (kMemo) if (memo_fits) {
+            lds.pcache[2 * i] = lo2 | (static_cast<u64>(hi2 - lo2) << 32);
+            lds.pcache[2 * i + 1] = lo3 | (static_cast<u64>(hi3 - lo3) << 32);
+          }
         }
         if constexpr (kDirect) {
           if (ix.direct_min != 0 && L <= kSortDepth && ix.planes[0] != nullptr) {
@@ -1022,6 +1057,21 @@ __device__ __forceinline__ void seed_pass(const DevIndex &ix, const WaveLds &lds
         chk3 = (hi3 - lo3) <= maxc || len3 >= spec_len;
         if (TALLY) wt.probes += probes;
       }
+      else if constexpr (kMemo) {
+        BucketFact f2, f3;
+        if (memo_hit) {
+          const u64 m2 = lds.pcache[2 * i], m3 = lds.pcache[2 * i + 1];
+          f2 = {static_cast<u32>(m2), static_cast<u32>(m2 >> 32)};
+          f3 = {static_cast<u32>(m3), static_cast<u32>(m3 >> 32)};
+        }
+        else {
+          f2.lo = ix.counter[k2]; f2.d = ix.counter[k2 + 1] - f2.lo;
+          f3.lo = cnt3[k3];       f3.d = cnt3[k3 + 1] - f3.lo;
+        }
+        const SensBounds b = sensitive_bounds(f2, f3, maxc);
+        chk2 = b.chk2; lo2 = b.lo2; hi2 = b.lo2 + b.n2;
+        chk3 = b.chk3; lo3 = b.lo3; hi3 = b.lo3 + b.n3;
+      }
       else {
         lo2 = ix.counter[k2]; hi2 = ix.counter[k2 + 1];
         lo3 = cnt3[k3];       hi3 = cnt3[k3 + 1];
@@ -1031,6 +1081,7 @@ __device__ __forceinline__ void seed_pass(const DevIndex &ix, const WaveLds &lds
       }
       if (TALLY) ++wt.seed_iters;
     }
+    if constexpr (kMemo) if (SPECIFIC && memo_fits) memo_n = min(g0 + 64u, n_off);  // (this block's live lanes have written)
     Segs sg;
     sg.na = chk2 ? hi2 - lo2 : 0u;
     sg.nb = chk3 ? hi3 - lo3 : 0u;
@@ -1205,6 +1256,14 @@ __device__ __forceinline__ void seed_pass(const DevIndex &ix, const WaveLds &lds
       if (TIMED) wt.t_replay += tc - td;
     }
   }
+}
+
+// (the pair kernels, whose sets append: no memo)
+template <bool SPECIFIC, bool TIMED, bool COOP, bool REC, class Set>
+__device__ __forceinline__ void seed_pass(const DevIndex &ix, const WaveLds &lds, u32 enc, bool g_to_a,
+                                          u32 flags, u32 L, Set &S, WorkTally &wt, u32 &seg_epoch) {
+  u32 memo_n = 0;
+  seed_pass<SPECIFIC, TIMED, COOP, REC>(ix, lds, enc, g_to_a, flags, L, S, wt, seg_epoch, memo_n);
 }
 
 // =============================================================================

@@ -12,6 +12,13 @@
 //            follows it directly in every form that has both (scratch_room; the long forms' two slots alone can be
 //            smaller than the histogram)
 //   hres     128 x u16 on lbest;  samp, and tier 1's scratch table (PeLds::tmp), on the cache;  the single-end fin on jpos
+//   memo     the record-fed single-end forms' base-bucket facts: one 16-byte slot (lo2, d2, lo3, d3) per seed offset of a
+//            call's specific pass, from the cache's first byte, written by the specific pass and read by the sensitive
+//            pass of the SAME (strand, alphabet) call (seed_pass, abm_seed_bounds.hpp).  Those forms keep no candidate
+//            cache, so the region is idle during their seed passes; kBoundsMemoSlots slots fit, 86 are ever used (the
+//            longest read of a record-fed launch).  tb -- the traceback table, then the SAM / BAM line -- takes the
+//            cache only after a read's last seed pass, and the next read's first specific pass writes before anything
+//            reads: the memo never outlives its call.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -46,6 +53,12 @@ constexpr u32 kSampSlots = 512;  // samp (u32)
 constexpr u32 kPeFinBytes = 2 * kSeCap * 4;
 static_assert(kStepSlots * sizeof(u16) <= kLaneSlots * sizeof(int), "hres lies on lbest");
 static_assert(kSampSlots * sizeof(u32) <= kCacheBytes, "samp lies on the window cache");
+// the bounds memo (see above): slots of two u64 (lo | d << 32 per table); the longest read the window records serve
+// (window_record_max_len of the five blocks build_wrec stops at) has kRecordMaxLen / 2 specific offsets
+constexpr u32 kBoundsMemoSlotBytes = 16;
+constexpr u32 kBoundsMemoSlots = kCacheBytes / kBoundsMemoSlotBytes;
+constexpr u32 kRecordMaxLen = 172;
+static_assert((kRecordMaxLen / 2) * kBoundsMemoSlotBytes <= kCacheBytes, "the bounds memo lies on the window cache");
 
 enum : int { kWhole = 0, kSeed = 1, kMate = 2 };  // the pair kernels' phases (abm_kernels_pe.hip)
 
