@@ -11,6 +11,7 @@ from .api import (  # noqa: F401
     SE_T_RICH, SE_A_RICH, SE_RANDOM, PE_NORMAL, PE_PBAT, PE_RANDOM, RECORDS_SAM, RECORDS_BAM,
     HIT_DTYPE, PAIR_DTYPE, EXPORTED_SYMBOLS,
     Inflater, bgzf_scan, BGZF_BLOCK_DTYPE, ERR_INFLATE,
+    Deflater, deflate_bgzf_host, bgzf_deflate_bound, ERR_CAPACITY,
     INFLATE_OK, INFLATE_HEADER, INFLATE_DATA, INFLATE_SIZE, INFLATE_CRC,
 )
 from .build import build  # noqa: F401

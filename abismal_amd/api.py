@@ -12,6 +12,7 @@ PE_NORMAL, PE_PBAT, PE_RANDOM = 0, 1, 2
 RECORDS_SAM, RECORDS_BAM = 0, 1
 INFLATE_OK, INFLATE_HEADER, INFLATE_DATA, INFLATE_SIZE, INFLATE_CRC = 0, 1, 2, 3, 4
 ERR_INFLATE = -3
+ERR_CAPACITY = -2
 
 HIT_DTYPE = np.dtype([("diffs", "<i2"), ("flags", "<u2"), ("pos", "<u4")])
 PAIR_DTYPE = np.dtype([("aln_score", "<i2"), ("reserved", "<i2"), ("r1", HIT_DTYPE), ("r2", HIT_DTYPE)])
@@ -27,6 +28,7 @@ EXPORTED_SYMBOLS = [
     "abm_ctx_set_pe_split", "abm_ctx_pe_split_stats", "abm_ctx_pe_timed_launches", "abm_ctx_last_forms", "abm_ctx_set_pair_phases", "abm_device_memory", "abm_ctx_pe_footprint", "abm_index_set_seed_extension_cap", "abm_ctx_pinned_bytes", "abm_ctx_set_sam_tails", "abm_ctx_slice_sam_tails", "abm_ctx_pe_sam_tails", "abm_ctx_set_record_format",
     "abm_index_set_window_records", "abm_ctx_window_records",
     "abm_bgzf_scan", "abm_inflater_create", "abm_inflater_destroy", "abm_inflate_bgzf", "abm_inflate_bgzf_device",
+    "abm_deflate_bgzf_bound", "abm_deflater_create", "abm_deflater_destroy", "abm_deflate_bgzf", "abm_deflate_bgzf_device", "abm_deflate_bgzf_host",
 ]
 
 
@@ -132,6 +134,15 @@ def load_library():
         lib.abm_inflater_destroy.argtypes = [vp]
         lib.abm_inflate_bgzf.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_uint64, vp]
         lib.abm_inflate_bgzf_device.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_uint64, vp, vp]
+    if hasattr(lib, "abm_deflate_bgzf"):
+        u64p = C.POINTER(C.c_uint64)
+        lib.abm_deflate_bgzf_bound.argtypes = [C.c_uint64, C.c_uint32]
+        lib.abm_deflate_bgzf_bound.restype = C.c_uint64
+        lib.abm_deflater_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        lib.abm_deflater_destroy.argtypes = [vp]
+        lib.abm_deflate_bgzf.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, u64p, vp, C.c_uint64, u64p]
+        lib.abm_deflate_bgzf_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, vp, vp, vp]
+        lib.abm_deflate_bgzf_host.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, u64p, vp, C.c_uint64, u64p]
     _lib = lib
     return lib
 
@@ -219,6 +230,70 @@ class Inflater:
     def inflate_device(self, d_comp, comp_bytes, d_blocks, n_blocks, d_text, text_bytes, d_status, stream=0):
         """abm_inflate_bgzf_device: all d_* are integer device addresses (e.g. tensor.data_ptr()); not synchronised"""
         _check(self._lib.abm_inflate_bgzf_device(self.handle, d_comp, comp_bytes, d_blocks, n_blocks, d_text, text_bytes, d_status, stream))
+
+
+def bgzf_deflate_bound(n, block_bytes=0):
+    """abm_deflate_bgzf_bound: bytes that surely hold the members of n bytes of text cut every block_bytes (0 = 0xff00)"""
+    lib = load_library()
+    if block_bytes > 0xff00:
+        lib.abm_deflate_bgzf_bound(int(n), int(block_bytes))
+        _check(-1)
+    return int(lib.abm_deflate_bgzf_bound(int(n), int(block_bytes)))
+
+
+def _deflate_call(call, data, block_bytes):
+    """one of abm_deflate_bgzf / abm_deflate_bgzf_host (the deflater already bound) over `data` -> (bytes, blocks)"""
+    buf = np.frombuffer(data, dtype=np.uint8)
+    cap = bgzf_deflate_bound(len(buf), block_bytes)
+    n_cap = -(-len(buf) // (block_bytes or 0xff00))
+    out = np.zeros(max(1, cap), dtype=np.uint8)
+    blocks = np.zeros(max(1, n_cap), dtype=BGZF_BLOCK_DTYPE)
+    n_out, n_blocks = C.c_uint64(), C.c_uint64()
+    _check(call(buf.ctypes.data if len(buf) else None, len(buf), int(block_bytes), out.ctypes.data, cap, C.byref(n_out),
+                blocks.ctypes.data, n_cap, C.byref(n_blocks)))
+    return out[:n_out.value].tobytes(), blocks[:n_blocks.value].copy()
+
+
+def deflate_bgzf_host(data, block_bytes=0):
+    """abm_deflate_bgzf_host: `data` (bytes) as BGZF members, one per block_bytes (0 = 0xff00) of it, encoded serially on
+    this thread; no end-of-file block.  Returns (bytes, blocks[BGZF_BLOCK_DTYPE])."""
+    return _deflate_call(load_library().abm_deflate_bgzf_host, data, block_bytes)
+
+
+class Deflater:
+    """abm_deflater_create / abm_deflater_destroy + abm_deflate_bgzf: text deflated into BGZF blocks on the device"""
+
+    def __init__(self, device=0):
+        self._lib = load_library()
+        h = C.c_void_p()
+        _check(self._lib.abm_deflater_create(int(device), C.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if self.handle:
+            self._lib.abm_deflater_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def deflate(self, data, block_bytes=0):
+        """abm_deflate_bgzf over `data` (bytes): (members end to end, blocks[BGZF_BLOCK_DTYPE]); the same bytes as
+        deflate_bgzf_host gives"""
+        return _deflate_call(lambda *a: self._lib.abm_deflate_bgzf(self.handle, *a), data, block_bytes)
+
+    def deflate_device(self, d_text, text_bytes, block_bytes, d_out, out_capacity, d_out_bytes, d_blocks, stream=0):
+        """abm_deflate_bgzf_device: all d_* are integer device addresses (e.g. tensor.data_ptr()); not synchronised"""
+        _check(self._lib.abm_deflate_bgzf_device(self.handle, d_text, text_bytes, block_bytes, d_out, out_capacity, d_out_bytes, d_blocks, stream))
 
 
 # letters of the seed-extension tables that Index() asks for when its caller does not say: None = the library's

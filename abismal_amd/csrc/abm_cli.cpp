@@ -135,6 +135,7 @@ constexpr unsigned kPeDeviceSamWorkers = 0;
 // interleaved runs each: DESIGN.md 4.5); ABM_CLI_DEVICE_SAM=1 turns them on.
 constexpr unsigned kSeDeviceBamWorkers = 0, kPeDeviceBamWorkers = 0;
 std::atomic<uint64_t> g_inflate_device_blocks{0}, g_inflate_host_blocks{0}, g_inflate_fallback_blocks{0};  // BGZF blocks of the input by who inflated them (fallback: the device rejected it, the host did not)
+std::atomic<uint64_t> g_deflate_device_blocks{0}, g_deflate_host_blocks{0}, g_deflate_fallback_blocks{0};  // BGZF blocks of -B output by who deflated them (fallback: the device call failed, the host redid its slice)
 std::atomic<uint64_t> g_device_records{0}, g_host_records{0};  // SAM / BAM records whose text the kernels / the formatters wrote
 
 // every ABM_CLI_* number: a positive value of the variable, else the default
@@ -163,6 +164,7 @@ struct RunPlan {
   uint64_t rec_bytes = 0;    // bytes per record of the first file (0: unknown)
   size_t reserve_reads = 0;
   bool stream_slices = false, device_sam = false;
+  bool device_deflate = false;  // -B at -z 1: the workers deflate a slice's records on the run's GPUs (ABM_CLI_DEVICE_DEFLATE)
   bool device_inflate = false;  // BGZF input: the workers inflate a chunk's blocks on the run's GPUs (ABM_CLI_DEVICE_INFLATE)
   int pe_text_per_gpu = 0;   // paired: contexts per GPU whose batches carry SAM text from the device
   int se_mode = 0, pe_mode = 0;
@@ -289,6 +291,10 @@ RunPlan make_plan(const Options &opt, const Topology &topo, const CpuQuota &quot
   // of them), =0 on the host; the host is the default.  Virtual GPUs have no device; other input ignores it.
   const char *where = std::getenv("ABM_CLI_DEVICE_INFLATE");
   p.device_inflate = where && where[0] == '1' && p.input == InputKind::Bgzf && !p.virtual_gpus;
+  // where -B output is deflated: ABM_CLI_DEVICE_DEFLATE=1 on the run's GPUs, dealt out as the inflaters are; the host is
+  // the default.  It stands in for the fast encoder alone (-z 1): levels 0 and 2..9 keep their meaning, on the host.
+  const char *deflate_where = std::getenv("ABM_CLI_DEVICE_DEFLATE");
+  p.device_deflate = deflate_where && deflate_where[0] == '1' && opt.bam && g_bgzf_level == 1 && !p.virtual_gpus;
   p.n_regions = std::max(1, opt.out_parts);
   if (p.n_regions > 1 && p.input != InputKind::PlainMapped && p.input != InputKind::PlainPread) throw std::runtime_error("-out-parts needs plain (seekable, uncompressed) FASTQ input");
   for (size_t e = 0; e < opt.reads.size(); ++e) {  // (a pipe is not read ahead of the run)
@@ -611,6 +617,7 @@ struct Pipeline {
   std::vector<RawPool> raw_pool;
   std::vector<LineFile> lf;
   bool count_gated = false;  // BGZF: inflating further ahead is on hold until slices have been written
+  std::vector<DeviceDeflate> deflaters;  // device deflate of -B output: likewise
   std::vector<DeviceBgzf> inflaters;  // device inflate: one per host worker, dealt round the run's GPUs; empty otherwise
   std::vector<std::unique_ptr<Batch>> live_batches;
   int mappers_live;
@@ -653,6 +660,10 @@ struct Pipeline {
     if (plan.device_inflate) {
       inflaters = std::vector<DeviceBgzf>(plan.n_host);
       for (unsigned t = 0; t < plan.n_host; ++t) inflaters[t].open(plan.dev_of[t % static_cast<unsigned>(plan.n_gpus)]);
+    }
+    if (plan.device_deflate) {
+      deflaters = std::vector<DeviceDeflate>(plan.n_host);
+      for (unsigned t = 0; t < plan.n_host; ++t) deflaters[t].open(plan.dev_of[t % static_cast<unsigned>(plan.n_gpus)]);
     }
     // ---- output files.  A slice's place is fixed in slice order; its region's writer pwrite()s it.
     // (Writes to one file take its inode lock, so they run one at a time; copying into a shared mapping of the file
@@ -1651,14 +1662,21 @@ struct Pipeline {
     }
   }
   // formats a slice; its place in its region's file is fixed once every earlier slice's size is known
-  void format_task(Slice *sl) {
+  // (`dev`: the calling worker's deflater with device deflate, else null)
+  void format_task(Slice *sl, DeviceDeflate *dev) {
     const auto t0 = now();
     format_slice(*sl);
     if (opt.bam) {  // (the block stream is built in a buffer the thread keeps, then trades places with the slice's text)
       thread_local RawBuf z;
       z.clear();
       z.reserve(sl->text.size() / 2 + (1u << 16));
-      bgzf_compress(sl->text, z);
+      // a device call that fails costs the run nothing: the slice goes through the host's encoder, and is counted
+      uint64_t n_blocks = (sl->text.size() + 0xff00 - 1) / 0xff00;
+      if (dev && dev->run(sl->text, z, n_blocks)) g_deflate_device_blocks += n_blocks;
+      else {
+        bgzf_compress(sl->text, z);
+        (dev ? g_deflate_fallback_blocks : g_deflate_host_blocks) += n_blocks;
+      }
       sl->text.swap(z);
     }
     const double dt = since(t0);
@@ -1714,7 +1732,7 @@ struct Pipeline {
           }
         }
         if (to_count) count_chunk(ce, ck, count_buf, inflaters.empty() ? nullptr : &inflaters[id]);
-        else if (to_format) format_task(to_format);
+        else if (to_format) format_task(to_format, deflaters.empty() ? nullptr : &deflaters[id]);
         else parse_slice(std::move(to_parse));
       }
     }
@@ -1886,6 +1904,7 @@ void write_timing_file(const Options &opt, const RunPlan &plan, const Topology &
      << ", \"sam_text_by\": \"" << (plan.device_sam ? "device" : "host") << "\", \"sam_records\": {\"device\": " << g_device_records.load() << ", \"host\": " << g_host_records.load() << "}, \"pe_text_contexts_per_gpu\": " << (plan.paired && plan.device_sam ? plan.pe_text_per_gpu : 0) << ", \"window_records_serve_reads_up_to\": " << (ctxs.empty() ? 0u : abm_ctx_window_records(ctxs[0])) << ", \"host_threads\": " << plan.n_host << ", \"numa_nodes\": " << plan.n_nodes << ", \"pinned\": " << (topo.pinning ? "true" : "false")
      << ", \"out_parts\": " << plan.n_regions << ", \"out_bytes\": " << pl.out_bytes << ", \"batches\": " << pl.n_batches << ", \"max_lead_in_records\": " << pl.max_lead << ", \"region_lead_in_scanned_records\": " << pl.region_lead_scanned << ", \"region_lead_in_records\": " << pl.region_lead_records
      << ", \"inflate\": {\"where\": \"" << (plan.device_inflate ? "device" : "host") << "\", \"device_blocks\": " << g_inflate_device_blocks.load() << ", \"host_blocks\": " << g_inflate_host_blocks.load() << ", \"fallback_blocks\": " << g_inflate_fallback_blocks.load() << "}"
+     << ", \"deflate\": {\"where\": \"" << (plan.device_deflate ? "device" : "host") << "\", \"device_blocks\": " << g_deflate_device_blocks.load() << ", \"host_blocks\": " << g_deflate_host_blocks.load() << ", \"fallback_blocks\": " << g_deflate_fallback_blocks.load() << "}"
      << ", \"batch_reads\": " << plan.batch_reads << ", \"host_ceiling\": " << (plan.virtual_gpus ? "true" : "false")
      << ", \"batches_per_gpu\": [";
   for (int g = 0; g < plan.n_gpus; ++g) tj << (g ? ", " : "") << pl.gpu_batches[g];
@@ -1995,6 +2014,7 @@ int main(int argc, char **argv) {
       return EXIT_SUCCESS;
     }
     if (cmd == "bgzf") {  // abismal-amd bgzf [-z n] <in> <out>: any file as BGZF blocks, the way -B output is compressed (a test hook)
+      // abismal-amd bgzf -device k <in> <out>: the same through abm_deflate_bgzf on that GPU (-z does not apply)
       // abismal-amd bgzf -d [-device k] <in> <out>: the other way round -- any BGZF file inflated whole, by the host's
       // BgzfInflater, or with -device by abm_inflate_bgzf on that GPU; a damaged block ends it and is named by its offset
       std::vector<std::string> pos;
@@ -2006,7 +2026,7 @@ int main(int argc, char **argv) {
         else if (std::string(argv[i]) == "-device" && i + 1 < argc) device = std::atoi(argv[++i]);
         else pos.push_back(argv[i]);
       }
-      if (pos.size() != 2) { std::cerr << "usage: abismal-amd bgzf [-z n] <in> <out>\n       abismal-amd bgzf -d [-device k] <in> <out>\n"; return EXIT_FAILURE; }
+      if (pos.size() != 2) { std::cerr << "usage: abismal-amd bgzf [-z n | -device k] <in> <out>\n       abismal-amd bgzf -d [-device k] <in> <out>\n"; return EXIT_FAILURE; }
       std::ifstream in(pos[0], std::ios::binary);
       if (!in) throw std::runtime_error("cannot open " + pos[0]);
       std::string raw((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>()), z;
@@ -2046,7 +2066,15 @@ int main(int argc, char **argv) {
         out.write(text.data(), static_cast<std::streamsize>(text.size()));
         return out ? EXIT_SUCCESS : EXIT_FAILURE;
       }
-      bgzf_compress(raw, z);
+      if (device < 0) bgzf_compress(raw, z);
+      else {
+        DeviceDeflate dev;
+        dev.open(device);
+        for (size_t at = 0; at < raw.size(); at += size_t(2048) * 0xff00) {  // (128 MB of text a call)
+          uint64_t n_blocks = 0;
+          if (!dev.run(raw.substr(at, size_t(2048) * 0xff00), z, n_blocks)) throw std::runtime_error(abm_last_error());
+        }
+      }
       static const unsigned char eof_block[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
       z.append(reinterpret_cast<const char *>(eof_block), 28);
       std::ofstream out(pos[1], std::ios::binary);

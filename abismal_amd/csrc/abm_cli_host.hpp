@@ -1,5 +1,5 @@
 // abismal-amd, host placement: the NUMA nodes and cores threads are pinned to, the container's CPU quota, what kind of
-// file an input is, the BGZF inflater, the SIGBUS handler of mapped input.  Part of abm_cli.cpp's one translation unit:
+// file an input is, the BGZF inflater and deflater on a GPU, the SIGBUS handler of mapped input.  Part of abm_cli.cpp's one translation unit:
 // everything here has internal linkage.
 #pragma once
 #include <fcntl.h>
@@ -189,6 +189,28 @@ struct DeviceBgzf {
     status.assign(blocks.size(), 0);
     const int rc = abm_inflate_bgzf(inf, comp, comp_bytes, blocks.data(), static_cast<uint32_t>(blocks.size()), text, text_bytes, status.data());
     if (rc != 0 && rc != ABM_ERR_INFLATE) throw std::runtime_error(abm_last_error());
+    return rc == 0;
+  }
+};
+
+// one thread's deflater on a GPU (the C ABI's abm_deflater: its own stream, device buffers and pinned staging)
+struct DeviceDeflate {
+  abm_deflater *def = nullptr;
+  DeviceDeflate() = default;
+  DeviceDeflate(const DeviceDeflate &) = delete;
+  ~DeviceDeflate() { if (def) abm_deflater_destroy(def); }
+  void open(int device) {
+    if (!def && abm_deflater_create(device, &def) != 0) throw std::runtime_error(abm_last_error());
+  }
+  // raw -> BGZF members appended to out (no end-of-file block); their number in n_blocks.  false: the call failed and out
+  // is as it was (the caller compresses on the host)
+  template <class A, class B> bool run(const A &raw, B &out, uint64_t &n_blocks) {
+    const size_t at0 = out.size();
+    const uint64_t cap = abm_deflate_bgzf_bound(raw.size(), 0);
+    uint64_t n_out = 0;
+    out.resize(at0 + cap);
+    const int rc = abm_deflate_bgzf(def, raw.data(), raw.size(), 0, &out[at0], cap, &n_out, nullptr, 0, &n_blocks);
+    out.resize(at0 + (rc == 0 ? n_out : 0));
     return rc == 0;
   }
 };

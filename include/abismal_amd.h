@@ -420,6 +420,47 @@ int abm_inflate_bgzf(abm_inflater *inf, const void *comp, uint64_t comp_bytes, c
 int abm_inflate_bgzf_device(abm_inflater *inf, const void *d_comp, uint64_t comp_bytes, const abm_bgzf_block *d_blocks, uint32_t n_blocks,
                             void *d_text, uint64_t text_bytes, uint8_t *d_status, void *stream);
 
+/* Text deflated into BGZF blocks on the device: abm_inflate_bgzf's mirror image (no reference counterpart: the reference
+ * compresses its BAM output through htslib on the host, src/abismal.cpp:513-543).  The text is cut every block_bytes
+ * (0 = 0xff00, the most a block may hold here) and every piece becomes one BGZF member, one wavefront per member: the
+ * 18-byte header with the BC subfield, ONE deflate block -- fixed Huffman codes (RFC 1951 3.2.6) over greedy matches of
+ * 4 to 258 bytes at most 32768 back, or a stored block where that would be longer than the piece + 5 bytes -- then CRC-32
+ * and ISIZE.  A member is at most its text + 31 bytes.  The members lie end to end; descriptor k says where member k is
+ * ([at, at + len) of the output) and which text it holds ([text_at, text_at + text_len)).  No end-of-file block is
+ * appended.  The bytes are a function of the text and block_bytes alone: the device, every deflater and
+ * abm_deflate_bgzf_host give the same. */
+typedef struct abm_deflater abm_deflater; /* one stream on one GPU + its grow-only device buffers and pinned staging */
+/* bytes that surely hold the members of text_bytes of text cut every block_bytes (0 = 0xff00; above 0xff00: returns 0
+ * with a message in abm_last_error()) */
+uint64_t abm_deflate_bgzf_bound(uint64_t text_bytes, uint32_t block_bytes);
+/* A deflater is independent of any abm_ctx and of any inflater; several on one device run side by side, each on its own
+ * stream.  Calls on one deflater are serialised.  Without a HIP device the call fails with a message. */
+int abm_deflater_create(int device, abm_deflater **out);
+void abm_deflater_destroy(abm_deflater *def);
+/* Host buffers (pageable is fine): upload, deflate, copy out; returns when the members are in out[0, *out_bytes).  blocks
+ * may be NULL (blocks_capacity 0); *n_blocks is the number of members.  text_bytes == 0: no member, *out_bytes == 0.
+ *   0                 done
+ *   ABM_ERR_CAPACITY  out_capacity or blocks_capacity is too small: *out_bytes / *n_blocks say what is needed, nothing
+ *                     was written to out or blocks
+ *   other < 0         the call itself failed (abm_last_error()): a null pointer or block_bytes above 0xff00 (checked
+ *                     before anything is launched), a HIP error */
+int abm_deflate_bgzf(abm_deflater *def, const void *text, uint64_t text_bytes, uint32_t block_bytes,
+                     void *out, uint64_t out_capacity, uint64_t *out_bytes,
+                     abm_bgzf_block *blocks, uint64_t blocks_capacity, uint64_t *n_blocks);
+/* The same with everything resident in HBM (d_* are device pointers), enqueued on `stream` (a hipStream_t; NULL = default
+ * stream) and not synchronised, as abm_inflate_bgzf_device: returns 0 once enqueued.  d_blocks holds one descriptor per
+ * member: ceil(text_bytes / block_bytes) of them.  *d_out_bytes is always what the members take; if that is more than
+ * out_capacity nothing at or beyond d_out + out_capacity is written.  The members are encoded in the deflater's own
+ * scratch memory, which a later call on the same deflater reuses: order such calls on one stream. */
+int abm_deflate_bgzf_device(abm_deflater *def, const void *d_text, uint64_t text_bytes, uint32_t block_bytes,
+                            void *d_out, uint64_t out_capacity, uint64_t *d_out_bytes,
+                            abm_bgzf_block *d_blocks, void *stream);
+/* The same encoder run serially on the calling thread, no device needed: the specification of the device's bytes.
+ * Arguments and results as abm_deflate_bgzf. */
+int abm_deflate_bgzf_host(const void *text, uint64_t text_bytes, uint32_t block_bytes,
+                          void *out, uint64_t out_capacity, uint64_t *out_bytes,
+                          abm_bgzf_block *blocks, uint64_t blocks_capacity, uint64_t *n_blocks);
+
 #ifdef __cplusplus
 }
 #endif
