@@ -146,7 +146,7 @@ size_t ext_scratch_bytes(int mode, u32 extra) {
 }
 
 hipError_t build_ext_table(const DevIndex &ix, int mode, u32 extra, u32 maxc, u64 n_idx, uint2 *out, void *scratch, u32 *d_fail,
-                           hipStream_t st) {
+                           hipStream_t st, u32 gap_cap) {
   const u64 n_keys = ext_keys(mode, extra), n_base = ext_keys(mode, 0);
   const u32 *index = mode == 0 ? ix.index : (mode == 1 ? ix.index_t : ix.index_a);
   const u32 *counter = mode == 0 ? ix.counter : (mode == 1 ? ix.counter_t : ix.counter_a);
@@ -158,7 +158,7 @@ hipError_t build_ext_table(const DevIndex &ix, int mode, u32 extra, u32 maxc, u6
   GapList gaps;
   gaps.count = reinterpret_cast<u32 *>(p); p += 64;
   gaps.rec = reinterpret_cast<u64 *>(p);
-  gaps.cap = kExtGapCap;
+  gaps.cap = std::min(gap_cap, kExtGapCap);  // (the scratch area holds kExtGapCap slots)
   hipError_t e = hipMemsetAsync(bad, 0, ((n_base + 31) / 32 + 1) * 4, st);
   if (e != hipSuccess) return e;
   e = hipMemsetAsync(gaps.count, 0, 64, st);

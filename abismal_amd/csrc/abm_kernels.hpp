@@ -179,12 +179,12 @@ static_assert(kSeCap * sizeof(u32) <= kSeCap * sizeof(u32), "the single-end fin 
 
 // seed-extension tables (abm_ext.hip): keys of table `mode` (0: 2-letter, 1 / 2: 3-letter C->T / G->A) with `extra`
 // letters beyond the hashed ones; bytes of scratch a build needs; the build itself (out[ext_keys] entries, n_idx =
-// entries of the table's index array)
+// entries of the table's index array; gap_cap: slots of the gap list, fewer than kExtGapCap only in tests)
 constexpr u32 kExtGapCap = 1u << 20;
 u64 ext_keys(int mode, u32 extra);
 size_t ext_scratch_bytes(int mode, u32 extra);
 hipError_t build_ext_table(const DevIndex &ix, int mode, u32 extra, u32 maxc, u64 n_idx, uint2 *out, void *scratch, u32 *d_fail,
-                           hipStream_t st);
+                           hipStream_t st, u32 gap_cap = kExtGapCap);
 // window records (DevIndex::wrec): the longest read records of `blocks` blocks serve (2 L - key weight <= 64 blocks: the
 // first seed offset's window must end, and the last one's begin, inside the record), the blocks a read length needs, the
 // bytes of the table, and the build (records of index, index_t, index_a one after the other; n_idx = their entries)

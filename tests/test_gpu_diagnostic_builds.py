@@ -419,7 +419,8 @@ def test_se_tallies_across_index_configurations(beds):
     from, never which offsets are walked, which buckets are checked or what enters the set: seed_offsets, candidates and
     set_updates are EXACTLY those of the plain configuration, for the whole batch (reads with two exact matches included: the
     kernel's stopping place is a function of the candidates' order alone).  The tables answer for most offsets with one
-    load in the place of bisections: 0 < probes <= plain's.  With direct narrowing the count is whatever narrow_direct's
+    load in the place of bisections: 0 < probes < plain's, strictly (tables that tabulate nothing would give equality; what the
+    tables hold is compared key by key in tests/test_gpu_index_derived.py).  With direct narrowing the count is whatever narrow_direct's
     own search takes: printed, non-zero."""
     bed = beds("rep")
     reads = bed.reads(0)
@@ -431,7 +432,7 @@ def test_se_tallies_across_index_configurations(beds):
         for k in ("seed_offsets", "candidates", "set_updates", "alignments"):
             assert w[k] == got["plain"][k] > 0, (name, k)
         assert w["search_probes"] > 0
-    assert got["tables"]["search_probes"] <= got["plain"]["search_probes"]
+    assert got["tables"]["search_probes"] < got["plain"]["search_probes"]
     assert got["records"]["search_probes"] == got["plain"]["search_probes"], "the single-end kernel bisects on the nibble array with records too"
     assert got["records"]["window_cache_hits"] == got["all"]["window_cache_hits"] == 0
     assert 0 < got["plain"]["window_cache_hits"] <= got["plain"]["candidates"]
