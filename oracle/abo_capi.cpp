@@ -18,7 +18,7 @@ template <class F> int guarded(F &&f) {
   try { f(); return 0; }
   catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
-constexpr int kWorkValues = 12;
+constexpr int kWorkValues = 16;
 struct MapperBox {
   const Index *ix;
   MapParams par;
@@ -99,15 +99,17 @@ void abo_mapper_free(void *p) { delete static_cast<MapperBox *>(p); }
 // Reads are trimmed ASCII, concatenated in `blob` with n+1 offsets.  Results:
 // out[i] as the reference's bests[i] just before format_se, CIGARs as BAM u32
 // ops in fixed slots of `cig_stride` per read with their count in cig_n[i].
-// work (optional, kWorkValues = 12 values) accumulates the Work tallies: the nine of the
-// algorithmic-bytes model, then the blank-nibble probes of the 2-letter and 3-letter tables and the probes the two
-// bisections of a 3-letter step share.  threads>1 splits the batch
+// work (optional, kWorkValues = 16 values) accumulates the Work tallies: the nine of the
+// algorithmic-bytes model, then the blank-nibble probes of the 2-letter and 3-letter tables, the probes the two
+// bisections of a 3-letter step share, and the four tallies of the paired-end set at its limit (pe_full_sets,
+// pe_lists_over_512, pe_lists_over_4096, pe_matings_skipped; zero for single-end).  threads>1 splits the batch
 // into contiguous shards, one Mapper per thread.
 int abo_map_se(void *mapper, int mode, uint64_t n, const char *blob, const uint64_t *off,
                abo_hit *out, uint32_t *cig, uint32_t cig_stride, uint32_t *cig_n,
                unsigned threads, uint64_t *work) {
   MapperBox *b = static_cast<MapperBox *>(mapper);
   std::atomic<int> bad{0};
+  std::string why;  // the first failing shard's message (written once, read after the join)
   std::vector<Work> works(std::max(1u, threads));
   auto shard = [&](unsigned t, uint64_t lo, uint64_t hi) {
     try {
@@ -129,7 +131,7 @@ int abo_map_se(void *mapper, int mode, uint64_t n, const char *blob, const uint6
       }
       works[t] = mp.work;
     }
-    catch (const std::exception &e) { bad = 1; }
+    catch (const std::exception &e) { if (!bad.exchange(1)) why = e.what(); }
   };
   const unsigned nt = std::max(1u, threads);
   std::vector<std::thread> th;
@@ -139,11 +141,12 @@ int abo_map_se(void *mapper, int mode, uint64_t n, const char *blob, const uint6
   if (work) {
     for (const Work &w : works) {
       const uint64_t v[kWorkValues] = {w.reads, w.seed_iters, w.search_probes, w.candidates, w.words, w.set_updates,
-                                       w.aligns, w.aligns_tb, w.dp_cells, w.blank_probes2, w.blank_probes3, w.shared_probes3};
+                                       w.aligns, w.aligns_tb, w.dp_cells, w.blank_probes2, w.blank_probes3, w.shared_probes3,
+                                       w.pe_full_sets, w.pe_lists_over_512, w.pe_lists_over_4096, w.pe_matings_skipped};
       for (int k = 0; k < kWorkValues; ++k) work[k] += v[k];
     }
   }
-  if (bad) { g_err = "oracle shard failed"; return -1; }
+  if (bad) { g_err = "oracle shard failed: " + why; return -1; }
   return 0;
 }
 
@@ -153,6 +156,7 @@ int abo_map_pe(void *mapper, int mode, uint64_t n, const char *blob1, const uint
                uint32_t *cig_n1, uint32_t *cig_n2, unsigned threads, uint64_t *work) {
   MapperBox *b = static_cast<MapperBox *>(mapper);
   std::atomic<int> bad{0};
+  std::string why;  // the first failing shard's message (written once, read after the join)
   std::vector<Work> works(std::max(1u, threads));
   auto shard = [&](unsigned t, uint64_t lo, uint64_t hi) {
     try {
@@ -188,7 +192,7 @@ int abo_map_pe(void *mapper, int mode, uint64_t n, const char *blob1, const uint
       }
       works[t] = mp.work;
     }
-    catch (const std::exception &e) { bad = 1; }
+    catch (const std::exception &e) { if (!bad.exchange(1)) why = e.what(); }
   };
   const unsigned nt = std::max(1u, threads);
   std::vector<std::thread> th;
@@ -198,11 +202,12 @@ int abo_map_pe(void *mapper, int mode, uint64_t n, const char *blob1, const uint
   if (work) {
     for (const Work &w : works) {
       const uint64_t v[kWorkValues] = {w.reads, w.seed_iters, w.search_probes, w.candidates, w.words, w.set_updates,
-                                       w.aligns, w.aligns_tb, w.dp_cells, w.blank_probes2, w.blank_probes3, w.shared_probes3};
+                                       w.aligns, w.aligns_tb, w.dp_cells, w.blank_probes2, w.blank_probes3, w.shared_probes3,
+                                       w.pe_full_sets, w.pe_lists_over_512, w.pe_lists_over_4096, w.pe_matings_skipped};
       for (int k = 0; k < kWorkValues; ++k) work[k] += v[k];
     }
   }
-  if (bad) { g_err = "oracle shard failed"; return -1; }
+  if (bad) { g_err = "oracle shard failed: " + why; return -1; }
   return 0;
 }
 

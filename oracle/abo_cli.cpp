@@ -378,6 +378,8 @@ int cmd_map(int argc, char **argv) {
       mapper.work.reads += w.reads; mapper.work.seed_iters += w.seed_iters; mapper.work.search_probes += w.search_probes;
       mapper.work.candidates += w.candidates; mapper.work.words += w.words; mapper.work.set_updates += w.set_updates;
       mapper.work.aligns += w.aligns; mapper.work.aligns_tb += w.aligns_tb; mapper.work.dp_cells += w.dp_cells;
+      mapper.work.pe_full_sets += w.pe_full_sets; mapper.work.pe_lists_over_512 += w.pe_lists_over_512;
+      mapper.work.pe_lists_over_4096 += w.pe_lists_over_4096; mapper.work.pe_matings_skipped += w.pe_matings_skipped;
     }
   }
   else {
@@ -447,7 +449,9 @@ int cmd_map(int argc, char **argv) {
     wo << "{\"reads\":" << w.reads << ",\"seconds\":" << secs << ",\"seed_iters\":" << w.seed_iters
        << ",\"search_probes\":" << w.search_probes << ",\"candidates\":" << w.candidates
        << ",\"words\":" << w.words << ",\"set_updates\":" << w.set_updates << ",\"aligns\":" << w.aligns
-       << ",\"aligns_tb\":" << w.aligns_tb << ",\"dp_cells\":" << w.dp_cells << "}\n";
+       << ",\"aligns_tb\":" << w.aligns_tb << ",\"dp_cells\":" << w.dp_cells
+       << ",\"pe_full_sets\":" << w.pe_full_sets << ",\"pe_lists_over_512\":" << w.pe_lists_over_512
+       << ",\"pe_lists_over_4096\":" << w.pe_lists_over_4096 << ",\"pe_matings_skipped\":" << w.pe_matings_skipped << "}\n";
   }
   return 0;
 }

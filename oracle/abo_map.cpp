@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <stdexcept>
 
 namespace abo {
 
@@ -127,6 +128,7 @@ struct PeSet {
   u32 sz = 1, capacity = kPeCapSmall;
   i16 cutoff = 0, good_cutoff = 0;
   bool sure_ambig = false;
+  Work *work = nullptr;
 
   bool full() const { return sz == capacity; }
   void begin_read(u32 readlen) {
@@ -151,11 +153,13 @@ struct PeSet {
       }
     }
     v[sz++] = Hit{d, flags, pos};
+    if (work && sz == kPeCapLarge) ++work->pe_full_sets;
     std::push_heap(v.begin(), v.begin() + sz, by_diffs);
     cutoff = specific ? std::min(cutoff, v[0].diffs) : v[0].diffs;
     sure_ambig = full() && cutoff == 0;
   }
   void sort_unique() {  // prepare_for_mating
+    if (work) { work->pe_lists_over_512 += sz > 512; work->pe_lists_over_4096 += sz > 4096; }
     std::sort(v.begin(), v.begin() + sz, [](const Hit &a, const Hit &b) { return a.pos < b.pos; });
     sz = static_cast<u32>(std::unique(v.begin(), v.begin() + sz,
                                       [](const Hit &a, const Hit &b) { return a.same_site(b); }) -
@@ -319,6 +323,7 @@ struct Mapper::Impl {
   Impl(const Index &i, const MapParams &p, Work &w) : ix(i), par(p), work(w) {
     aln.genome = ix.genome.data();
     aln.work = &w;
+    pe[0].work = pe[1].work = &w;
   }
 
   // src/abismal.cpp:1105-1122
@@ -524,6 +529,10 @@ struct Mapper::Impl {
       while (ia != na && A.v[ia].pos + par.max_frag < frag_end) ++ia;
       for (; ia != na && A.v[ia].pos + par.min_frag <= frag_end && !best.sure_ambig(); ++ia) {
         const Hit ha = A.v[ia];
+        // the rewind above stops at entry 0, the empty entry (position 0), which is in reach of a hit within max_frag of the
+        // genome's first base: the reference aligns it as a partner and reads before its genome (oracle/README.md)
+        if (ha.empty())
+          throw std::runtime_error("a candidate lies within max_frag of the genome's first base: the mating is undefined there");
         if (sb == 0)
           sb = aln.run<false>(hb.diffs, mdb, qb.nib.data(), qb.len, hb.pos);
         if (memo[ia] == 0) {
@@ -585,6 +594,8 @@ struct Mapper::Impl {
       B.sort_unique();
       mate(endA == 1, A, B, qa, qb, ciga, cigb, best);
     }
+    else
+      ++work.pe_matings_skipped;
     for (int e : {endA, endB}) {
       const PeSet &P = pe[e];
       SeSet &S = se[e];

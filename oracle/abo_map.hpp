@@ -63,6 +63,10 @@ struct Work {
   // first of every step.  An implementation that runs the two side by side loads that letter once: its probe count is
   // search_probes - shared_probes3 (what the GPU kernels' diagnostic builds tally)
   u64 shared_probes3 = 0;
+  // the paired-end set at its limit of 32768 entries: admissions that bring a set to that size, sort_unique calls entered
+  // with more than 512 and more than 4096 entries, and orientation calls whose mating is skipped because an end's set is
+  // full at cutoff 0 (worth_aligning).  All zero unless max_candidates is raised far beyond its default
+  u64 pe_full_sets = 0, pe_lists_over_512 = 0, pe_lists_over_4096 = 0, pe_matings_skipped = 0;
 };
 
 using Cigar = std::vector<u32>;

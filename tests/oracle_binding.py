@@ -15,7 +15,8 @@ CLI = os.path.join(ORACLE_DIR, "_build", "abismal_oracle")
 HIT_DTYPE = np.dtype([("diffs", "<i2"), ("flags", "<u2"), ("pos", "<u4")])
 PAIR_DTYPE = np.dtype([("aln_score", "<i2"), ("reserved", "<i2"), ("r1", HIT_DTYPE), ("r2", HIT_DTYPE)])
 WORK_KEYS = ["reads", "seed_iters", "search_probes", "candidates", "words", "set_updates", "aligns",
-             "aligns_tb", "dp_cells", "blank_probes2", "blank_probes3", "shared_probes3"]
+             "aligns_tb", "dp_cells", "blank_probes2", "blank_probes3", "shared_probes3",
+             "pe_full_sets", "pe_lists_over_512", "pe_lists_over_4096", "pe_matings_skipped"]
 
 
 def build_oracle():

@@ -37,10 +37,17 @@ INDEXES = {
     "rep_targets": ("rep.fa", 20, "targets.bed"),
     "plain": ("plain.fa", 20, None),          # the genome of test_windows_that_reach_into_an_n_run: no IUPAC letters
     "trex": ("tRex1.fa", 20, None),           # the reference's own fixture, for the long reads
+    "sat": ("sat.fa", 20, None),              # one family of 30000 copies at 2.5 % divergence (synth.satellite_genome)
+    "sat_exact": ("sat_exact.fa", 20, None),  # the same family without divergence
 }
 
 SE, SE12, SET = ["se.fq"], ["se_w12.fq"], ["se_targets.fq"]
 PE, PBAT, MIX = ["pe_1.fq", "pe_2.fq"], ["pbat_1.fq", "pbat_2.fq"], ["mix_1.fq", "mix_2.fq"]
+SAT, SAT_EXACT = ["sat_1.fq", "sat_2.fq"], ["sat_exact_1.fq", "sat_exact_2.fq"]
+# the satellite cases' own floor: 64 pairs and 256 reads go in, every one of them cut from the family; at least 64 records
+# must come out (and, with -a on the family without divergence, at least 64 of them flagged secondary)
+SAT_PAIRS, SAT_READS, SAT_MIN_RECORDS = 64, 256, 64
+SAT_FAMILY = dict(copies=30000, unit_len=200, lead=41000, seed=5)  # (lead: beyond -L 40000 plus an end, see synth.pairs_on_satellite)
 
 
 def _case(name, index, reads, flags=(), **more):
@@ -83,6 +90,16 @@ CASES = [
     # idx -A targets: reads from inside, across and outside the regions
     _case("targets_se", "rep_targets", SET),
     _case("targets_pe", "rep_targets", ["pe_targets_1.fq", "pe_targets_2.fq"]),
+    # -c 30000 on the satellite family: paired-end candidate sets at their limit of 32768 entries (the fixture of
+    # tests/test_gpu_pe_full_sets.py: 64 pairs of 2 x 100, 256 reads), mating windows of about 180 partners with -L 40000,
+    # and the family without divergence, whose full sets at cutoff 0 make the reference skip the mating
+    _case("pe_c30000", "sat", SAT, ["-c", "30000"], min_records=SAT_MIN_RECORDS),
+    _case("pe_c30000_L40000", "sat", SAT, ["-c", "30000", "-L", "40000"], min_records=SAT_MIN_RECORDS),
+    _case("pe_R_c30000", "sat", ["sat_mix_1.fq", "sat_mix_2.fq"], ["-R", "-c", "30000"], min_records=SAT_MIN_RECORDS),  # every other pair swapped
+    # (without -a the family without divergence gives no record at all -- every end is ambiguous: the statistics file is the answer)
+    _case("pe_c30000_exact", "sat_exact", SAT_EXACT, ["-c", "30000"], min_records=0),
+    _case("pe_a_c30000_exact", "sat_exact", SAT_EXACT, ["-a", "-c", "30000"], min_records=SAT_MIN_RECORDS, min_secondary=SAT_MIN_RECORDS),
+    _case("se_c30000", "sat", ["sat_se.fq"], ["-c", "30000"], min_records=SAT_MIN_RECORDS),
 ]
 
 MIN_RECORDS, MIN_GHOST_READS, MIN_SECONDARY, MIN_LONG_MAPPED = 500, 1000, 50, 2
@@ -245,6 +262,17 @@ def make_inputs(wd):
     write_fastq(p("long_1.fq"), q1[:150] + l1 + q1[150:]); write_fastq(p("long_2.fq"), q2[:150] + l2 + q2[150:])
     write_fastq(p("too_long.fq"), pad[:20] + _from_chroms(trex, [TOO_LONG], seed=11) + pad[20:40])
 
+    # the satellite family (tests/test_gpu_pe_full_sets.py's genomes and reads)
+    near = synth.satellite_genome(p("sat.fa"), divergence=0.025, **SAT_FAMILY)
+    exact = synth.satellite_genome(p("sat_exact.fa"), divergence=0.0, **SAT_FAMILY)
+    t1, t2 = synth.pairs_on_satellite(near, p("sat.fa"), SAT_PAIRS, 100, seed=7, max_frag=40000)
+    write_fastq(p("sat_1.fq"), t1); write_fastq(p("sat_2.fq"), t2)
+    write_fastq(p("sat_mix_1.fq"), [y if i % 2 else x for i, (x, y) in enumerate(zip(t1, t2))])
+    write_fastq(p("sat_mix_2.fq"), [x if i % 2 else y for i, (x, y) in enumerate(zip(t1, t2))])
+    e1, e2 = synth.pairs_on_satellite(exact, p("sat_exact.fa"), SAT_PAIRS, 100, seed=7, max_frag=40000, planted=0.0)
+    write_fastq(p("sat_exact_1.fq"), e1); write_fastq(p("sat_exact_2.fq"), e2)
+    write_fastq(p("sat_se.fq"), synth.reads_on_satellite(near, p("sat.fa"), SAT_READS, 100, seed=11))
+
     names = sorted({f for c in CASES for f in c["reads"]} | {g for g, _, _ in INDEXES.values()} | {"targets.bed"})
     return {n: md5_file(p(n)) for n in names}
 
@@ -364,10 +392,10 @@ def record(wd):
             assert r.returncode == 0, f"{case['name']}: the reference failed:\n{r.stdout}"
             entry.update(digest(prefix))
             fields = _mapped_fields(prefix)
-            assert entry["records"] >= MIN_RECORDS, f"{case['name']}: only {entry['records']} records"
+            assert entry["records"] >= case.get("min_records", MIN_RECORDS), f"{case['name']}: only {entry['records']} records"
             if "-a" in case["flags"]:
                 sec = sum(1 for f in fields if int(f[1]) & 0x100)
-                assert sec >= MIN_SECONDARY, f"{case['name']}: only {sec} records with flag 0x100"
+                assert sec >= case.get("min_secondary", MIN_SECONDARY), f"{case['name']}: only {sec} records with flag 0x100"
             if case.get("long_reads"):
                 n_long = sum(1 for f in fields if len(f[9]) >= 5000)
                 assert n_long >= MIN_LONG_MAPPED, f"{case['name']}: only {n_long} mapped reads of 5000 bases or more"

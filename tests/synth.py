@@ -189,6 +189,101 @@ def mutated_pairs(fasta, n, L, seed, mut=0.02, bis=0.95, frag=(120, 600)):
     return out1, out2
 
 
+# ---- one satellite family of tens of thousands of copies: paired-end candidate sets at their limit of 32768 entries -----
+def satellite_genome(path, copies, unit_len, divergence, lead, seed, iupac=0):
+    """One chromosome of random sequence without N: `lead` bases, then `copies` copies of one random unit of unit_len
+    bases, evenly spaced at unit_len + 20, each with its own substitutions at `divergence`, all on one strand, then `lead`
+    bases more.  iupac: that many ambiguity letters in the two flanks, none inside the family (the genome then has no bit
+    planes).  With max_candidates raised to 30000 a read cut from a copy finds every copy: its candidate set fills.
+    The mating reaches back max_frag bases from a hit: pairs_on_satellite asserts that the first copy lies further in than
+    that (oracle/README.md, "Hits near the genome's first base").  Returns the layout pairs_on_satellite and
+    reads_on_satellite cut from."""
+    rng = np.random.default_rng(seed)
+    step = unit_len + 20
+    n = 2 * lead + copies * step
+    seq = ACGT[rng.integers(0, 4, n)].copy()
+    unit = ACGT[rng.integers(0, 4, unit_len)]
+    starts = lead + step * np.arange(copies)
+    fam = np.tile(unit, (copies, 1))
+    m = rng.random(fam.shape) < divergence
+    fam[m] = ACGT[rng.integers(0, 4, int(m.sum()))]
+    for at, piece in zip(starts, fam):
+        seq[at:at + unit_len] = piece
+    if iupac:
+        at = np.concatenate([rng.integers(0, lead - 1000, iupac // 2), n - lead + 1000 + rng.integers(0, lead - 1000, iupac - iupac // 2)])
+        seq[at] = np.frombuffer(b"RYMKSWBDHV", dtype=np.uint8)[rng.integers(0, 10, iupac)]
+    assert not (seq == ord("N")).any()
+    with open(path, "wb") as f:
+        f.write(b">sat\n" + b"\n".join(bytes(seq[i:i + 70]) for i in range(0, n, 70)) + b"\n")
+    return {"lead": lead, "copies": copies, "unit_len": unit_len, "step": step}
+
+
+def _planted(s, rng, subs, indel):
+    """up to `subs` substitutions, and with indel one base dropped or one inserted, away from the ends; length kept"""
+    s = s.copy()
+    L = len(s)
+    at = rng.integers(0, L, int(rng.integers(1, subs + 1))) if subs else []
+    for j in at:
+        s[j] = ACGT[(int(np.searchsorted(ACGT, s[j])) + int(rng.integers(1, 4))) % 4]
+    if indel:
+        j = int(rng.integers(25, L - 25))
+        s = np.concatenate([s[:j], s[j + 1:], s[-1:]]) if rng.random() < 0.5 else np.concatenate([s[:j], ACGT[rng.integers(0, 4, 1)], s[j:-1]])
+    return s
+
+
+def pairs_on_satellite(lay, fasta, n, L, seed, max_frag=3000, planted=0.5, indels=0.25, same_strand=0.125):
+    """n fully converted pairs of 2 x L from a satellite_genome: the fragment is one copy (unit_len bases, L <= unit_len),
+    end 1 its first L bases C -> T, end 2 the reverse complement of its last L bases (so G -> A).  A share `planted` of
+    the pairs carries 1-3 substitutions per end, a share `indels` of those a one-base insertion or deletion per end as well
+    (winners that need the DP and a gapped traceback).  A share `same_strand` has end 2 NOT reverse-complemented: its ends
+    find their copies in different orientation calls, so it can only be reported end by end (fallback hits only), from
+    full sets.  max_frag: the largest fragment limit the pairs will be mapped with -- the first copy must lie further in."""
+    assert lay["lead"] > max_frag + L, "the mating would reach the genome's first base: raise lead"
+    assert L <= lay["unit_len"]
+    rng = np.random.default_rng(seed)
+    ch = read_chroms(fasta)[0]
+    r1, r2 = [], []
+    for k in rng.choice(lay["copies"], n, replace=False):
+        at = lay["lead"] + int(k) * lay["step"]
+        f = ch[at:at + lay["unit_len"]]
+        a, b = f[:L], f[-L:]
+        if rng.random() < planted:
+            ind = rng.random() < indels
+            a, b = _planted(a, rng, 3, ind), _planted(b, rng, 3, ind)
+        a = a.copy()
+        a[a == ord("C")] = ord("T")
+        if rng.random() < same_strand:
+            b = b.copy()
+            b[b == ord("G")] = ord("A")
+        else:
+            b = COMP[b[::-1]]
+            b[b == ord("G")] = ord("A")
+        r1.append(bytes(a).decode())
+        r2.append(bytes(b).decode())
+    return r1, r2
+
+
+def reads_on_satellite(lay, fasta, n, L, seed, ragged=0.3, planted=0.5):
+    """n single-end reads from a satellite_genome, fully C -> T converted, every other one from the other strand; a share
+    `ragged` is cut to 47 ... L - 1 bases, a share `planted` carries 1-3 substitutions"""
+    rng = np.random.default_rng(seed)
+    ch = read_chroms(fasta)[0]
+    out = []
+    for i, k in enumerate(rng.choice(lay["copies"], n, replace=False)):
+        at = lay["lead"] + int(k) * lay["step"] + int(rng.integers(0, lay["unit_len"] - L + 1))
+        s = ch[at:at + L]
+        if rng.random() < planted:
+            s = _planted(s, rng, 3, False)
+        if i % 2:
+            s = COMP[s[::-1]]
+        if rng.random() < ragged:
+            s = s[: int(rng.integers(47, L))]
+        s = s.copy()
+        s[s == ord("C")] = ord("T")
+        out.append(bytes(s).decode())
+    return out
+
+
 # ---- repeat copies cut short by N runs: bucket narrowing where the probed letters are blank -----------------------------
 def repeats_against_n_runs(path, seed=17, n_chroms=2, chrom_len=130_000, n_full=160, n_trunc=40, fwd_frac=0.85,
                            div=(0.01, 0.02), fam_len=300, run_len=300, unit=10):
