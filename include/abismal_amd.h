@@ -357,7 +357,8 @@ int abm_ctx_take_score_iterations(abm_ctx *ctx, uint64_t out[2]);
 int abm_ctx_set_read_cycles(abm_ctx *ctx, uint32_t *d_read_cycles);
 /* Paired-end diagnostic kernels only: device array [n][8] (zeroed by the caller) to which the kernels that mate a pair add
  * its shader cycles / 1024 by phase -- probe + narrow, window gather + Hamming, replay, sort + unique, scoring of the
- * pairable entries, mating + tracebacks, best_single, single-end fallback (NULL = off). */
+ * pairable entries, mating + tracebacks, best_single, single-end fallback (NULL = off).  A phase whose two stamps come
+ * out in the wrong order (the counter has been seen to step back under a wave that is resident for long) adds 0. */
 int abm_ctx_set_pair_phases(abm_ctx *ctx, uint32_t *d_pair_phases);
 
 /* Measurement hook: when enabled, every main mapping-kernel launch is bracketed by

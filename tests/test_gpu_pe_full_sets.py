@@ -27,7 +27,7 @@ Every test first asserts, on the ORACLE's output alone, that its fixture is aliv
 written there).  The first copy lies LEAD = 41000 bases into the chromosome, beyond the largest max_frag used here (40000)
 plus an end: nearer than that the mating is undefined (oracle/README.md) and no test here goes there.
 
-Routes of the split launch (read off PeSet::append / admit, abm_pe_set.hpp, and emit_list, abm_kernels_pe.hip): in the seed
+Routes of the split launch (read off PeSet::append / admit, abm_pe_set.hpp, and emit_list, abm_pe_wave.hpp): in the seed
 kernel a list may grow to seed_cap entries, and abm_ctx_set_pe_split refuses a seed_cap beyond 16384; a list that wants
 more sets `overflow`, hence need_big, and the pair is the whole-pair kernel's.  A set that fills has 32768 > 16384 entries,
 so under every split form a pair with a full set is counted in mapped_whole, never in mated_from_device_memory; a staging
@@ -39,7 +39,8 @@ Seeded defects (each built into a copy of the library, this module run against i
   worth forced true (a full set at cutoff 0 is mated all the same): the 8 tests of test_exact_family fail, nothing else;
   one sample in fifty of sample_list 300 bases too high when samp_shift >= 5: NOT caught -- a search then starts a
       mating window one or two entries early, a partner less than 300 bases beyond max_frag, which has to win or tie a
-      pair to show.  Errors of an entry or two at a window's far edge are below what this fixture sees."""
+      pair to show.  Errors of an entry or two at a window's far edge are below what this fixture sees
+      (test_gpu_pe_mating_steps.py runs the searches alone and catches it)."""
 import concurrent.futures
 import os
 
