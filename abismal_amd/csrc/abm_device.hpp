@@ -87,11 +87,11 @@ struct DevIndex {
   u32 n_chroms;
 };
 constexpr u32 kSortDepth = 256;  // letters a bucket is sorted by (src/AbismalIndex.hpp: seed::n_sorting_positions)
-// direct narrowing of big ranges (narrow_direct, abm_kernels_core.hpp): the pair kernels, ranges of at least kDirectMin entries
+// direct narrowing of big ranges (narrow_direct, abm_seed.hpp): the pair kernels, ranges of at least kDirectMin entries
 #ifndef ABM_PE_DIRECT_NARROWING
 #define ABM_PE_DIRECT_NARROWING true
 #endif
-// (the single-end kernel: ABM_SE_DIRECT_NARROWING, abm_kernels_core.hpp)
+// (the single-end kernel: ABM_SE_DIRECT_NARROWING, abm_seed.hpp)
 #ifndef ABM_PE_DIRECT_MIN
 #define ABM_PE_DIRECT_MIN 64  // (2x150 at hg38 scale, round 5's kernels: 6.11-6.38 M reads/s at 64, 6.04-6.26 at 128, profiles/r05_exp_final_knobs.log; round 3's kernels had their best at 128: profiles/r03_exp_pe_direct_threshold.log)
 #endif

@@ -4,7 +4,7 @@
 // read; see DESIGN.md for the data layout and the reasoning.
 #include <type_traits>
 #include <utility>
-#include "abm_kernels_core.hpp"
+#include "abm_align.hpp"
 #include "abm_sam.hpp"
 
 

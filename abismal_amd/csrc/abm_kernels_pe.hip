@@ -15,7 +15,7 @@
 // wave per pair with 32768-entry sets in global memory (tier 2).
 #include <climits>
 #include <utility>
-#include "abm_kernels_core.hpp"
+#include "abm_align.hpp"
 #include "abm_pe_set.hpp"
 #include "abm_pe_wave.hpp"
 #include "abm_sam.hpp"

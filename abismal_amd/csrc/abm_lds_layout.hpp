@@ -1,5 +1,5 @@
 // abismal_amd: the one description of each mapping kernel's dynamic LDS (one allocation per wave), shared by the kernels
-// that carve it (se_carve in abm_kernels_core.hpp, pe_carve in abm_pe_set.hpp), the launchers that ask for its bytes
+// that carve it (se_carve in abm_seed.hpp, pe_carve in abm_pe_set.hpp), the launchers that ask for its bytes
 // and plain host C++ (tests/cpp/lds_layout_check.cpp).  No HIP runtime calls.
 //
 // A layout function walks the regions in their order once.  Its position type P is either u32 -- byte offsets from the

@@ -1,7 +1,7 @@
 // abismal_amd: the paired-end candidate set (pe_candidates, src/abismal.cpp:775-863) of one wave -- a header of
 // its own so that tests/hip/pe_set_check.hip can drive it against libstdc++ without compiling the mapping kernels.
 #pragma once
-#include "abm_kernels_core.hpp"
+#include "abm_seed.hpp"
 
 namespace abm {
 

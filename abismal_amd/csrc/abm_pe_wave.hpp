@@ -2,7 +2,7 @@
 // tests/hip/pe_mate_check.hip can drive the mating steps one by one without compiling the 36 mapping kernels.
 #pragma once
 #include <climits>
-#include "abm_kernels_core.hpp"
+#include "abm_align.hpp"
 #include "abm_pe_set.hpp"
 #include "abm_sam.hpp"
 

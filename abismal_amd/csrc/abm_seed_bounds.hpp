@@ -1,5 +1,5 @@
 // abismal_amd: what the sensitive seed pass checks at one seed offset, as a function of what is known of the offset's two
-// base buckets -- shared by seed_pass (abm_kernels_core.hpp) and plain host C++ (tests/cpp/sensitive_bounds_check.cpp).
+// base buckets -- shared by seed_pass (abm_seed.hpp) and plain host C++ (tests/cpp/sensitive_bounds_check.cpp).
 // No HIP runtime calls.
 //
 // The sensitive pass (process_seeds, src/abismal.cpp:1352-1371) looks at the base buckets only: the 2-letter bucket

@@ -1,7 +1,8 @@
 // GPU test program (built and run by tests/test_gpu_narrowing_at_n_runs.py): the kernels' three ways of narrowing a
 // bucket -- narrow_both<false> (letters from the nibble array), narrow_both<true> (letters from the window records, back
 // to the nibble array where a record's N flag is set or the probe is beyond its reach: record_nibble) and narrow_direct
-// followed by what seed_pass does with it (the result if `ok`, else the letter loop: restated here) -- against a plain restatement of
+// followed by what seed_pass does with it (the result if `ok`, else the letter loop: the kernel's own narrow_direct_chains,
+// abm_seed.hpp, run here as seed_pass runs it) -- against a plain restatement of
 // find_candidates / find_candidates_three (src/abismal.cpp:1163-1259): std::lower_bound letter by letter on the nibble
 // array, and the step back when the range empties.
 //
@@ -50,28 +51,20 @@ __global__ __launch_bounds__(64) void run(DevIndex ix, const Case *cases, u32 n,
   const bool g_to_a = c.g_to_a != 0;
   const u32 *idx3 = g_to_a ? ix.index_a : ix.index_t;
   const u32 rec3 = g_to_a ? ix.wrec_a0 : ix.wrec_t0;
+  // the call as the kernel's stage sees it: a read of qbase + limit bases (so that its limit at offset qbase is the case's)
+  SeedCall sc = {};
+  sc.qpk = qpk; sc.qb = qb; sc.idx3 = idx3; sc.rec3 = rec3;
+  sc.W = kW; sc.n_bits = 64u * kWB; sc.L = c.qbase + c.limit; sc.maxc = c.maxc; sc.g_to_a = g_to_a;
   Out o = {};
   for (int v = 0; v < 3; ++v) {
     u32 lo2 = c.lo, hi2 = c.hi, len2 = kKeyWeight, lo3 = c.lo, hi3 = c.hi, len3 = kKeyWeight3, probes = 0;
     bool run2 = true, run3 = true;
     if (v == 2) {
-      // seed_pass's rule (abm_kernels_core.hpp, "direct narrowing of big ranges"), restated: reads up to kSortDepth bases, ranges
-      // of at least direct_min entries and more than maxc, a chain not yet at its limit; the result counts only if ok
-      const u32 L = c.qbase + c.limit;
-      if (ix.direct_min != 0 && L <= kSortDepth && ix.planes[0] != nullptr) {
-        const DirectArgs da = {ix.planes[0], ix.nmap, qb, qpk, 64u * kWB, kW, L, c.maxc};
-        for (int chain = 0; chain < 2; ++chain) {
-          const bool three = chain != 0;
-          const u32 clo = three ? lo3 : lo2, chi = three ? hi3 : hi2, clen = three ? len3 : len2;
-          if (chi - clo >= ix.direct_min && chi - clo > c.maxc && clen < c.limit) {
-            const DirectRange r = narrow_direct(three ? (g_to_a ? 2 : 1) : 0, da, three ? idx3 : ix.index, c.qbase, c.limit, clo, chi, clen);
-            if (r.ok) {
-              if (three) { lo3 = r.lo; hi3 = r.hi; len3 = r.len; run3 = false; }
-              else { lo2 = r.lo; hi2 = r.hi; len2 = r.len; run2 = false; }
-            }
-          }
-        }
-      }
+      // the kernel's own rule for where narrow_direct is tried and what is taken from it (narrow_direct_chains, abm_seed.hpp)
+      Chains ch = {lo2, hi2, len2, lo3, hi3, len3, run2, run3};
+      narrow_direct_chains(ix, sc, c.qbase, ch, probes);
+      lo2 = ch.lo2; hi2 = ch.hi2; len2 = ch.len2; run2 = ch.run2;
+      lo3 = ch.lo3; hi3 = ch.hi3; len3 = ch.len3; run3 = ch.run3;
       o.open[0] = run2; o.open[1] = run3;
     }
     if (v == 0) narrow_both<false>(ix, idx3, g_to_a, qb, 64u * kWB, qpk, c.qbase, c.limit, c.maxc, run2, lo2, hi2, len2, run3, lo3, hi3, len3, probes, rec3);

@@ -40,7 +40,7 @@ ABM_STATUS_CIGAR_OVERFLOW / _SET_OVERFLOW makes the call map again or fail -- so
 slots and arena.  (The raw arena is not comparable between two runs of ANY build: waves take their room in it with an
 atomic add, in whatever order they finish, and a slot's first word holds where.)
 
-Tally relations (section "tallies"): each test's docstring derives its relation from seed_pass (abm_kernels_core.hpp) and
+Tally relations (section "tallies"): each test's docstring derives its relation from seed_pass (abm_seed.hpp) and
 Impl::seed_passes (oracle/abo_map.cpp) and says whether it is exact or a two-sided bound."""
 import os
 import time

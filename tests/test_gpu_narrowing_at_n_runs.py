@@ -28,9 +28,10 @@ Which builds these catch -- each tried once on a copy of the tree, every configu
     are found through their other seeds.
  2. window_records_kernel never sets the flag: narrow_check fails at once (the records' flags are compared with the nibble
     array entry by entry); end to end exactly the cases of 1.
- 3. seed_pass takes narrow_direct's result whatever `ok` says: narrow_check restates seed_pass's rule (it cannot call
-    seed_pass), so the change made to seed_pass alone does not reach it; made to the restated rule as well, narrow_check
-    fails at its first case.  End to end the change to seed_pass fails 114 of the 144 single-end configurations and 108 of
+ 3. seed_pass takes narrow_direct's result whatever `ok` says: when this was tried narrow_check restated seed_pass's rule,
+    so the change made to seed_pass alone did not reach it; made to the restated rule as well, narrow_check failed at its
+    first case.  (It now runs the kernel's own narrow_direct_chains, abm_seed.hpp, which is where such a change would be
+    made.)  End to end the change to seed_pass fails 114 of the 144 single-end configurations and 108 of
     the 144 paired-end ones in which the threshold is 16 or 64, every launch form (whose threshold is the default, 64), and
     none with direct narrowing off."""
 import os
