@@ -27,6 +27,7 @@ EXPORTED_SYMBOLS = [
     "abm_device_count", "abm_host_alloc", "abm_host_free", "abm_index_set_seed_extension", "abm_index_set_max_candidates", "abm_index_set_direct_narrowing", "abm_ctx_seed_extension", "abm_ctx_rebuild_seed_extension", "abm_device_numa_node",
     "abm_ctx_set_pe_split", "abm_ctx_pe_split_stats", "abm_ctx_pe_timed_launches", "abm_ctx_last_forms", "abm_ctx_set_pair_phases", "abm_device_memory", "abm_ctx_pe_footprint", "abm_index_set_seed_extension_cap", "abm_ctx_pinned_bytes", "abm_ctx_set_sam_tails", "abm_ctx_slice_sam_tails", "abm_ctx_pe_sam_tails", "abm_ctx_set_record_format",
     "abm_index_set_window_records", "abm_ctx_window_records",
+    "abm_index_set_iupac_planes", "abm_ctx_plane_chunks",
     "abm_bgzf_scan", "abm_inflater_create", "abm_inflater_destroy", "abm_inflate_bgzf", "abm_inflate_bgzf_device",
     "abm_deflate_bgzf_bound", "abm_deflater_create", "abm_deflater_destroy", "abm_deflate_bgzf", "abm_deflate_bgzf_device", "abm_deflate_bgzf_host",
 ]
@@ -309,7 +310,7 @@ DEFAULT_WINDOW_RECORDS = None
 class Index:
     """abm_index_open / abm_index_close."""
 
-    def __init__(self, path, seed_extension=None, window_records=None):
+    def __init__(self, path, seed_extension=None, window_records=None, iupac_planes=None):
         self._lib = load_library()
         h = C.c_void_p()
         _check(self._lib.abm_index_open(os.fsencode(path), C.byref(h)))
@@ -320,6 +321,8 @@ class Index:
         wrec = window_records if window_records is not None else DEFAULT_WINDOW_RECORDS
         if wrec is not None:
             self.set_window_records(wrec)
+        if iupac_planes is not None:
+            self.set_iupac_planes(iupac_planes)
         n = self._lib.abm_index_n_chroms(h)
         self.chrom_names = [self._lib.abm_index_chrom_name(h, i).decode() for i in range(n)]
         st = self._lib.abm_index_chrom_starts(h)
@@ -332,6 +335,12 @@ class Index:
         """abm_index_set_window_records: the index carries its candidates' windows for reads up to this length (0: none)"""
         self._lib.abm_index_set_window_records.argtypes = [C.c_void_p, C.c_int]
         _check(self._lib.abm_index_set_window_records(self.handle, int(max_read_len)))
+
+    def set_iupac_planes(self, on):
+        """abm_index_set_iupac_planes: a genome with IUPAC letters keeps its bit planes, the chunks around those letters
+        going back to the nibble array (before the first context is created; the library's default is off)"""
+        self._lib.abm_index_set_iupac_planes.argtypes = [C.c_void_p, C.c_int]
+        _check(self._lib.abm_index_set_iupac_planes(self.handle, 1 if on else 0))
 
     def set_seed_extension_cap(self, letters2, letters3):
         """abm_index_set_seed_extension_cap: the automatic table depths, capped (before the first context is created)"""
@@ -373,6 +382,14 @@ class Context:
         a, b, n = C.c_uint32(), C.c_uint32(), C.c_uint64()
         _check(self._lib.abm_ctx_seed_extension(self.handle, C.byref(a), C.byref(b), C.byref(n)))
         return int(a.value), int(b.value), int(n.value)
+
+    def plane_chunks(self):
+        """abm_ctx_plane_chunks: (4096-base chunks of the genome's bit planes, those of them sent back to the nibble array
+        because a blank or an IUPAC letter is within reach); (0, 0) without planes"""
+        n, f = C.c_uint64(), C.c_uint64()
+        self._lib.abm_ctx_plane_chunks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        _check(self._lib.abm_ctx_plane_chunks(self.handle, C.byref(n), C.byref(f)))
+        return int(n.value), int(f.value)
 
     def rebuild_seed_extension(self, max_candidates=0):
         """abm_ctx_rebuild_seed_extension: the device's tables rebuilt for another max_candidates (set-up call)"""

@@ -120,6 +120,7 @@ struct DeviceReplica {
   void *ext_mem[3] = {nullptr, nullptr, nullptr};  // seed-extension tables (abm_ext.hip), built for dix.ext_maxc candidates
   void *wrec_mem = nullptr;                         // window records (DevIndex::wrec)
   uint64_t plane_blocks = 0;                        // blocks of one bit-plane copy (guard blocks included)
+  uint64_t plane_chunks = 0, plane_flagged = 0;     // nmap: the genome's chunks, and those sent back to the nibble array (abm_ctx_plane_chunks)
   abm::u32 ext_tried = 0;                           // max_candidates of the last build attempt (it may have built nothing)
   double ext_build_s = 0;
   std::mutex mu;  // guards arena / refs / tables: the replicas of different devices are set up side by side
@@ -134,6 +135,7 @@ struct abm_index {
   int want_e2 = -1, want_e3 = -1;  // letters of the seed-extension tables; -1 = chosen from the index's size
   int cap_e2 = 7, cap_e3 = 4;      // ... but no more than these (abm_index_set_seed_extension_cap)
   int wrec_len = 0;                // window records for reads of up to this many bases (abm_index_set_window_records); 0 = none
+  bool iupac_planes = false;       // a genome with IUPAC letters keeps its bit planes, the letters marked like blanks (abm_index_set_iupac_planes)
   mutable std::mutex mu;  // guards the map itself and the wishes below (a replica's contents: DeviceReplica::mu)
   mutable std::map<int, DeviceReplica> replicas;  // by device ordinal; nodes stay for the index's lifetime
   uint32_t want_maxc = 0;  // max_candidates the tables are built for; 0 = the index file's
@@ -377,7 +379,8 @@ LaunchShape launch_shape(const abm_ctx *ctx, abm::u32 max_len, double valid_frac
   s.tb_extra = lng ? 0u : abm::tb_extra_bytes(s.GW, s.eff_len, s.size_frac);
   s.ctmp_cap = s.eff_len + 2;
   // cooperative window loads from the genome's bit planes (hamming_planes): not for genomes with IUPAC letters (no
-  // planes; their admission rule needs full_compare's word-by-word running sums) nor for reads beyond 448 bases;
+  // planes; their admission rule needs full_compare's word-by-word running sums -- unless abm_index_set_iupac_planes
+  // keeps the planes and sends the windows near such letters back to those sums) nor for reads beyond 448 bases;
   // G lanes x 64 bases cover a window of eff_len + 63 bases, and pairs start at four lanes.
   // ABM_COOP_WINDOWS=0 switches them off, =4 widens the single-end launch's two lanes to four (experiments)
   if (!lng && ctx->dix.planes[0] != nullptr) {
@@ -1132,6 +1135,15 @@ uint32_t abm_max_read_length(void) { return abm::kMaxReadLen; }
 uint64_t abm_ctx_reads_too_long(abm_ctx *ctx) { return ctx ? ctx->too_long : 0; }
 uint32_t abm_ctx_window_records(const abm_ctx *ctx) { return ctx && ctx->dix.wrec != nullptr ? ctx->dix.wrec_max_len : 0u; }
 int abm_ctx_filter_on_planes(const abm_ctx *ctx) { return ctx && ctx->dix.planes[0] != nullptr ? 1 : 0; }
+int abm_ctx_plane_chunks(const abm_ctx *ctx, uint64_t *chunks, uint64_t *flagged) {
+  return guarded([&] {
+    if (!ctx) throw std::invalid_argument("ctx is null");
+    const bool on = ctx->dix.planes[0] != nullptr;
+    std::lock_guard<std::mutex> lk(ctx->rep->mu);
+    if (chunks) *chunks = on ? ctx->rep->plane_chunks : 0;
+    if (flagged) *flagged = on ? ctx->rep->plane_flagged : 0;
+  });
+}
 
 int abm_index_open(const char *path, abm_index **out) {
   return guarded([&] {
@@ -1178,6 +1190,15 @@ int abm_index_set_window_records(abm_index *ix, int max_read_len) {
     std::lock_guard<std::mutex> lk(ix->mu);
     for (auto &r : ix->replicas) if (r.second.refs) throw std::invalid_argument("set the window records before the first context is created");
     ix->wrec_len = std::max(0, max_read_len);
+  });
+}
+
+int abm_index_set_iupac_planes(abm_index *ix, int on) {
+  return guarded([&] {
+    if (!ix) throw std::invalid_argument("index is null");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    for (auto &r : ix->replicas) if (r.second.refs) throw std::invalid_argument("set the IUPAC planes before the first context is created");
+    ix->iupac_planes = on != 0;
   });
 }
 
@@ -1264,7 +1285,8 @@ int abm_ctx_create(const abm_index *ix, int device, abm_ctx **out) {
       {
         DeviceReplica *rep_p;
         abm::u32 tables_maxc;
-        { std::lock_guard<std::mutex> lk(ix->mu); rep_p = &ix->replicas[device]; tables_maxc = ix->want_maxc ? ix->want_maxc : ix->h.max_candidates; }
+        bool iupac_planes;
+        { std::lock_guard<std::mutex> lk(ix->mu); rep_p = &ix->replicas[device]; tables_maxc = ix->want_maxc ? ix->want_maxc : ix->h.max_candidates; iupac_planes = ix->iupac_planes; }
         DeviceReplica &rep = *rep_p;
         std::lock_guard<std::mutex> lk(rep.mu);
         if (rep.refs == 0) {
@@ -1280,7 +1302,8 @@ int abm_ctx_create(const abm_index *ix, int device, abm_ctx **out) {
           for (int k = 0; k < 7; ++k) { offs[k] = total; total += up(sz[k] + 64); }
           // the filter's bit-plane copies of the genome (DevIndex::planes), derived on the device
           const uint64_t n_bases = h.chrom_starts.empty() ? 0 : h.chrom_starts.back();
-          const uint64_t n_blocks = h.multibit_genome ? 0 : (n_bases + abm::kPlaneBlock - 1) / abm::kPlaneBlock + 16;
+          const bool mark_multi = h.multibit_genome && iupac_planes;  // (IUPAC letters marked in nmap and the records, chunk by chunk)
+          const uint64_t n_blocks = h.multibit_genome && !mark_multi ? 0 : (n_bases + abm::kPlaneBlock - 1) / abm::kPlaneBlock + 16;
           for (int k = 7; k < 9; ++k) { offs[k] = total; total += up(n_blocks * 16 + 128); }
           const uint64_t nmap_words = n_blocks ? ((n_bases >> abm::kPlaneChunkBits) + 64) / 32 + 1 : 0;
           offs[9] = total; total += up(nmap_words * 4 + 64);
@@ -1310,6 +1333,8 @@ int abm_ctx_create(const abm_index *ix, int device, abm_ctx **out) {
             rep.dix.min_len = abm::kKeyWeight + h.window - 1;
             rep.dix.planes[0] = rep.dix.planes[1] = nullptr;
             rep.dix.nmap = nullptr;
+            rep.dix.multibit = 0;
+            rep.plane_blocks = rep.plane_chunks = rep.plane_flagged = 0;
             {
               char *ct = base + offs[10];
               HIPCHK(hipMemcpy(ct, h.chrom_starts.data(), (n_chr + 1) * 4, hipMemcpyHostToDevice));
@@ -1324,10 +1349,18 @@ int abm_ctx_create(const abm_index *ix, int device, abm_ctx **out) {
               auto *p0 = reinterpret_cast<abm::u64 *>(base + offs[7]), *p1 = reinterpret_cast<abm::u64 *>(base + offs[8] + 64);
               abm::u32 *d_bad = reinterpret_cast<abm::u32 *>(base + offs[8]);  // (the first 64 bytes of copy 1's array are free)
               auto *nmap = reinterpret_cast<abm::u32 *>(base + offs[9]);
-              HIPCHK(abm::launch_make_planes(rep.dix.genome, h.genome.size(), n_bases, n_blocks, p0, p1, nmap, d_bad, nullptr));
+              HIPCHK(abm::launch_make_planes(rep.dix.genome, h.genome.size(), n_bases, n_blocks, p0, p1, nmap, d_bad, nullptr, mark_multi ? 1u : 0u));
               abm::u32 bad = 0;
               HIPCHK(hipMemcpy(&bad, d_bad, 4, hipMemcpyDeviceToHost));
-              if (!bad) { rep.dix.planes[0] = p0; rep.dix.planes[1] = p1; rep.dix.nmap = nmap; rep.plane_blocks = n_blocks; }
+              if (!bad || mark_multi) {
+                rep.dix.planes[0] = p0; rep.dix.planes[1] = p1; rep.dix.nmap = nmap; rep.plane_blocks = n_blocks;
+                rep.dix.multibit = bad ? 1u : 0u;
+                // how much of the genome goes back to the nibble array: the flagged chunks among those the genome has
+                rep.plane_chunks = (n_bases + (uint64_t(1) << abm::kPlaneChunkBits) - 1) >> abm::kPlaneChunkBits;
+                std::vector<abm::u32> marks((rep.plane_chunks + 31) / 32, 0u);
+                if (!marks.empty()) HIPCHK(hipMemcpy(marks.data(), nmap, marks.size() * 4, hipMemcpyDeviceToHost));
+                for (uint64_t c = 0; c < rep.plane_chunks; ++c) rep.plane_flagged += (marks[c >> 5] >> (c & 31u)) & 1u;
+              }
               if (const char *e = experiment_env("ABM_PLANES_COPIES")) if (e[0] == '1') rep.dix.planes[1] = p0;
             }
           }

@@ -41,6 +41,8 @@ struct Options {
   int ext2 = -1, ext3 = -1;  // -seed-ext a,b: letters of the seed-extension tables (default: chosen from the index's size)
   int window_records = -1;   // -window-records L: the index's window records serve reads of up to L bases (0 = none; default: the
                              // longest of the input's first reads -- abm_index_set_window_records)
+  bool iupac_planes = false;  // -iupac-planes (or ABM_CLI_IUPAC_PLANES=1): a genome with IUPAC letters keeps its bit planes and window
+                              // records, the chunks around those letters going back to the nibble array (abm_index_set_iupac_planes)
   bool skip_long = false;     // -skip-long: reads the library reports as beyond its supported length are written unmapped
                               // (and counted in the warning) instead of failing the run
   bool host_ceiling = false;  // -host-ceiling / -virtual-gpus N (diagnostic): no device and no mapping call; every "GPU" hands
@@ -92,6 +94,7 @@ Options parse_map(int argc, char **argv) {
     }
     else if (k == "out-parts") o.out_parts = std::stoi(need(i));
     else if (k == "skip-long") o.skip_long = true;
+    else if (k == "iupac-planes") o.iupac_planes = true;
     else if (k == "window-records") o.window_records = std::max(0, std::stoi(need(i)));
     else if (k == "seed-ext") { const std::string v = need(i); if (std::sscanf(v.c_str(), "%d,%d", &o.ext2, &o.ext3) != 2) throw std::runtime_error("-seed-ext wants two numbers: a,b"); }
     else if (k == "timing") o.timing = need(i);  // JSON: reads, seconds (first batch submitted -> last byte written), stage busy times
@@ -362,6 +365,9 @@ void configure_index(abm_index *ix, const Options &opt, const RunPlan &plan) {
   // window records for reads as long as the input's: the longest of each file's first 256 (a batch with a longer read
   // than the records serve is filtered from the bit planes, as without them)
   if (abm_index_set_window_records(ix, opt.window_records < 0 ? plan.longest_len : opt.window_records) != 0) die_abm("window records");
+  // (off unless asked for, like the other device paths not yet measured at scale)
+  const char *iupac_env = std::getenv("ABM_CLI_IUPAC_PLANES");
+  if ((opt.iupac_planes || (iupac_env && iupac_env[0] != '0' && iupac_env[0] != '\0')) && abm_index_set_iupac_planes(ix, 1) != 0) die_abm("IUPAC planes");
 }
 // One replica of the index per device, per_gpu contexts on each ([g * per_gpu + k]); paired input: as many as fit.
 // false: the message has been printed.
@@ -1898,10 +1904,12 @@ void write_stats_file(const Options &opt, const RunPlan &plan, const Stats3 &tot
 void write_timing_file(const Options &opt, const RunPlan &plan, const Topology &topo, const CpuQuota &quota, const Pipeline &pl, const Report &rep,
                        const std::vector<abm_ctx *> &ctxs) {
   if (opt.timing.empty()) return;
+  uint64_t plane_chunks = 0, plane_flagged = 0;  // (the chunks of the genome's bit planes, and those that go back to the nibble array)
+  if (!ctxs.empty()) (void)abm_ctx_plane_chunks(ctxs[0], &plane_chunks, &plane_flagged);
   std::ofstream tj(opt.timing);
   tj << "{\"records\": " << rep.total_records << ", \"reads\": " << (plan.paired ? 2 : 1) * rep.total_records << ", \"seconds\": " << pl.secs
      << ", \"index_load_s\": " << rep.index_load_s << ", \"host_prepare_s\": " << pl.host_prepare_s << ", \"gpus\": " << plan.n_gpus << ", \"mappers_per_gpu\": " << plan.per_gpu
-     << ", \"sam_text_by\": \"" << (plan.device_sam ? "device" : "host") << "\", \"sam_records\": {\"device\": " << g_device_records.load() << ", \"host\": " << g_host_records.load() << "}, \"pe_text_contexts_per_gpu\": " << (plan.paired && plan.device_sam ? plan.pe_text_per_gpu : 0) << ", \"window_records_serve_reads_up_to\": " << (ctxs.empty() ? 0u : abm_ctx_window_records(ctxs[0])) << ", \"host_threads\": " << plan.n_host << ", \"numa_nodes\": " << plan.n_nodes << ", \"pinned\": " << (topo.pinning ? "true" : "false")
+     << ", \"sam_text_by\": \"" << (plan.device_sam ? "device" : "host") << "\", \"sam_records\": {\"device\": " << g_device_records.load() << ", \"host\": " << g_host_records.load() << "}, \"pe_text_contexts_per_gpu\": " << (plan.paired && plan.device_sam ? plan.pe_text_per_gpu : 0) << ", \"window_records_serve_reads_up_to\": " << (ctxs.empty() ? 0u : abm_ctx_window_records(ctxs[0])) << ", \"plane_chunks\": " << plane_chunks << ", \"plane_chunks_flagged\": " << plane_flagged << ", \"host_threads\": " << plan.n_host << ", \"numa_nodes\": " << plan.n_nodes << ", \"pinned\": " << (topo.pinning ? "true" : "false")
      << ", \"out_parts\": " << plan.n_regions << ", \"out_bytes\": " << pl.out_bytes << ", \"batches\": " << pl.n_batches << ", \"max_lead_in_records\": " << pl.max_lead << ", \"region_lead_in_scanned_records\": " << pl.region_lead_scanned << ", \"region_lead_in_records\": " << pl.region_lead_records
      << ", \"inflate\": {\"where\": \"" << (plan.device_inflate ? "device" : "host") << "\", \"device_blocks\": " << g_inflate_device_blocks.load() << ", \"host_blocks\": " << g_inflate_host_blocks.load() << ", \"fallback_blocks\": " << g_inflate_fallback_blocks.load() << "}"
      << ", \"deflate\": {\"where\": \"" << (plan.device_deflate ? "device" : "host") << "\", \"device_blocks\": " << g_deflate_device_blocks.load() << ", \"host_blocks\": " << g_deflate_host_blocks.load() << ", \"fallback_blocks\": " << g_deflate_fallback_blocks.load() << "}"

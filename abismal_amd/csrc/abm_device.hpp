@@ -85,6 +85,12 @@ struct DevIndex {
   const u32 *chrom_name_off;  // [n_chroms + 1] into chrom_names
   const char *chrom_names;
   u32 n_chroms;
+  // Planes of a genome with IUPAC letters (abm_index_set_iupac_planes): 1 = some nibbles have two or more bits.  Such a
+  // nibble's plane code is arbitrary and, unlike a blank, it can match where the code does not: nmap and the records'
+  // flags mark them as they mark blanks, and the filters redo marked candidates BEFORE the cutoff test.  Uniform; 0 for
+  // every other genome, whose kernels then run as they always did.  (The struct's last member, so that no other member
+  // moves: profiles/iupac_planes_resources_diff.txt.)
+  u32 multibit;
 };
 constexpr u32 kSortDepth = 256;  // letters a bucket is sorted by (src/AbismalIndex.hpp: seed::n_sorting_positions)
 // direct narrowing of big ranges (narrow_direct, abm_seed.hpp): the pair kernels, ranges of at least kDirectMin entries

@@ -183,7 +183,7 @@ hipError_t build_ext_table(const DevIndex &ix, int mode, u32 extra, u32 maxc, u6
 __global__ __launch_bounds__(256) void window_records_kernel(const u64 *__restrict__ planes0, u64 n_plane_blocks,
                                                              const u64 *__restrict__ genome, u64 n_bases,
                                                              const u32 *__restrict__ index, u64 n_entries, u64 first_record,
-                                                             u32 blocks, u32 back, u64 *__restrict__ out) {
+                                                             u32 blocks, u32 back, u64 *__restrict__ out, u32 mark_multi) {
   const u64 t = static_cast<u64>(blockIdx.x) * blockDim.x + threadIdx.x;
   const u64 e = t / blocks;
   const u32 b = static_cast<u32>(t % blocks);
@@ -198,7 +198,8 @@ __global__ __launch_bounds__(256) void window_records_kernel(const u64 *__restri
   if (s) { lo |= plane(k + 1, 0) << (64 - s); hi |= plane(k + 1, 1) << (64 - s); }
   if (b == blocks - 1) {
     // the record's spare base (its last: 2 max_len - key weight = 64 blocks - 1 bases are ever looked at) says whether
-    // the stretch holds a blank nibble, which two bits cannot express: the narrowing probes ask (record_nibble)
+    // the stretch holds a blank nibble (mark_multi: or one with two or more bits), which two bits cannot express: the
+    // narrowing probes ask (record_nibble), and on such genomes the filter (filter_step_records)
     lo &= ~(1ull << 63); hi &= ~(1ull << 63);
     const long long first = static_cast<long long>(index[e]) - static_cast<long long>(back), end = first + 64ll * blocks - 1;
     bool blank = false;
@@ -211,8 +212,21 @@ __global__ __launch_bounds__(256) void window_records_kernel(const u64 *__restri
       if (upto < 16) part &= (1ull << (4 * upto)) - 1;
       part &= ~((1ull << (4 * from)) - 1);
       if ((~ones & part) != 0) blank = true;
+      if (mark_multi) {  // (a nibble with two or more bits: its plane code is arbitrary)
+        const u64 sum = (w & 0x1111111111111111ull) + ((w >> 1) & 0x1111111111111111ull) + ((w >> 2) & 0x1111111111111111ull) +
+                        ((w >> 3) & 0x1111111111111111ull);
+        if ((sum & (part * 14ull)) != 0) blank = true;
+      }
       q += upto - from;
     }
+    // (mark_multi: full_compare sums whole 16-base words, the read's last one padded with 0xF, and a multi-bit nibble
+    // under that padding counts -1 or -2 where a one-hot or a blank one cannot lower the sum: the up to 15 bases a window's
+    // last word reaches past the stretch are the filter's business as well)
+    if (mark_multi)
+      for (long long q = end < 0 ? 0 : end; q < end + 15 && static_cast<u64>(q) < n_bases && !blank; ++q) {
+        const u32 nb = static_cast<u32>(genome[q >> 4] >> ((q & 15) << 2)) & 15u;
+        if ((nb & (nb - 1)) != 0) blank = true;
+      }
     if (blank) lo |= 1ull << 63;
   }
   u64 *o = out + 2 * ((first_record + e) * blocks + b);
@@ -234,7 +248,7 @@ hipError_t build_window_records(const DevIndex &ix, u64 n_plane_blocks, u64 n_ba
     const u64 threads = n_idx[m] * blocks;
     if (threads)
       hipLaunchKernelGGL(window_records_kernel, dim3(static_cast<u32>((threads + 255) / 256)), dim3(256), 0, st, ix.planes[0], n_plane_blocks,
-                         ix.genome, n_bases, arrays[m], n_idx[m], first, blocks, back, out);
+                         ix.genome, n_bases, arrays[m], n_idx[m], first, blocks, back, out, ix.multibit);
     first += n_idx[m];
   }
   return hipGetLastError();

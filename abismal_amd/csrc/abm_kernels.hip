@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void pack_reads_kernel(const char *__restrict_
 // =============================================================================
 __global__ __launch_bounds__(256) void make_planes_kernel(const u64 *__restrict__ genome, u64 n_words, u64 n_bases,
                                                           u64 n_blocks, u64 *__restrict__ p0, u64 *__restrict__ p1,
-                                                          u32 *__restrict__ nmap, u32 *__restrict__ bad) {
+                                                          u32 *__restrict__ nmap, u32 *__restrict__ bad, u32 mark_multi) {
   const u64 b = static_cast<u64>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (b >= n_blocks) return;
   u64 lo = 0, hi = 0;
@@ -85,7 +85,9 @@ __global__ __launch_bounds__(256) void make_planes_kernel(const u64 *__restrict_
   p0[2 * b] = lo; p0[2 * b + 1] = hi;
   p1[2 * b] = lo; p1[2 * b + 1] = hi;
   if (multi) atomicOr(bad, 1u);
-  if (blank) {
+  // (mark_multi: an IUPAC letter is one more nibble that two bits cannot express -- its code here is arbitrary -- and is
+  // marked like a blank one; the caller decides from `bad` whether planes with such letters are used at all)
+  if (blank || (multi && mark_multi)) {
     // a window that starts up to kPlaneReach bases before this block can see the blank
     const u64 at = b * kPlaneBlock, from = at >= kPlaneReach ? at - kPlaneReach : 0;
     for (u64 c = from >> kPlaneChunkBits; c <= (at + kPlaneBlock - 1) >> kPlaneChunkBits; ++c)
@@ -609,10 +611,10 @@ hipError_t launch_se(SeForm f, const SeArgs &a, size_t lds, u32 grid, hipStream_
 }
 
 hipError_t launch_make_planes(const u64 *d_genome, u64 n_words, u64 n_bases, u64 n_blocks, u64 *d_planes0,
-                              u64 *d_planes1, u32 *d_nmap, u32 *d_bad, hipStream_t st) {
+                              u64 *d_planes1, u32 *d_nmap, u32 *d_bad, hipStream_t st, u32 mark_multi) {
   if (n_blocks == 0) return hipSuccess;
   hipLaunchKernelGGL(make_planes_kernel, dim3(static_cast<u32>((n_blocks + 255) / 256)), dim3(256), 0, st, d_genome,
-                     n_words, n_bases, n_blocks, d_planes0, d_planes1, d_nmap, d_bad);
+                     n_words, n_bases, n_blocks, d_planes0, d_planes1, d_nmap, d_bad, mark_multi);
   return hipGetLastError();
 }
 

@@ -192,11 +192,13 @@ u32 window_record_max_len(u32 blocks);
 u32 window_record_blocks_for(u32 max_len);
 size_t window_record_bytes(u64 n_entries, u32 blocks);
 hipError_t build_window_records(const DevIndex &ix, u64 n_plane_blocks, u64 n_bases, const u64 n_idx[3], u32 blocks, u64 *out, hipStream_t st);
+// (ix.multibit: a record's flag also tells of nibbles with two or more bits in its stretch)
 // bit-plane copies of the genome for the Hamming filter (DevIndex::planes): n_blocks blocks of 64 bases each,
 // from the first n_words words of nibbles; blank nibbles (N) mark their surroundings in nmap (DevIndex::nmap,
-// zeroed by the caller); *bad is set if a nibble below n_bases has two or more bits
+// zeroed by the caller); *bad is set if a nibble below n_bases has two or more bits (an IUPAC letter); mark_multi: such
+// nibbles mark nmap as blank ones do
 hipError_t launch_make_planes(const u64 *d_genome, u64 n_words, u64 n_bases, u64 n_blocks, u64 *d_planes0,
-                              u64 *d_planes1, u32 *d_nmap, u32 *d_bad, hipStream_t st);
+                              u64 *d_planes1, u32 *d_nmap, u32 *d_bad, hipStream_t st, u32 mark_multi = 0);
 hipError_t launch_pack_reads(const char *d_blob, const u64 *d_off, u64 n, u32 W, u64 *d_packed,
                              u32 *d_lens, hipStream_t st);
 hipError_t launch_order_reads(const DevIndex &ix, const u64 *d_packed, const u32 *d_lens, u64 n, u32 W,

@@ -726,7 +726,8 @@ __device__ __forceinline__ long long phase_stamp() {
 // at all, except for the few candidates whose distance is within the cutoff: those alone need a position -- for the
 // set, and to ask whether an N is within reach of the window (the planes' distance never exceeds the true one -- a blank
 // nibble matches nothing, the planes' code 0 there may match -- so a candidate beyond the cutoff on the planes is beyond
-// it on the nibble array too).  No position cache either: a repeated window costs a third of a line, not a line.
+// it on the nibble array too; not so for IUPAC letters, DevIndex::multibit, whose candidates the record's flag picks out
+// before the cutoff test).  No position cache either: a repeated window costs a third of a line, not a line.
 //
 // The bounds memo (REC, single-end): the sensitive pass looks the first max(window, L/2) offsets up again, with the keys the
 // specific pass of the same call has just used on the same lanes, and of a base bucket it needs only the exact range, or that
@@ -936,11 +937,13 @@ __device__ __forceinline__ OffsetBuckets offset_buckets(const DevIndex &ix, cons
 
 // ---- stage 3, per step of 128 candidates: filter, then replay in order -----------------------------------------
 // rare: the distances of the lanes whose window has an N within reach (na / nb) are redone on the nibble array, where
-// an N is an N
-__device__ __forceinline__ void redo_on_nibbles(const DevIndex &ix, const SeedCall &sc, u32 na, u32 pa, int &ha, u32 nb, u32 pb, int &hb) {
+// an N is an N -- and an IUPAC letter (DevIndex::multibit) an IUPAC letter: such a letter can make a word's share
+// negative, so a redone candidate carries its own largest prefix sum (hma / hmb), which admission follows
+__device__ __forceinline__ void redo_on_nibbles(const DevIndex &ix, const SeedCall &sc, u32 na, u32 pa, int &ha, int &hma, u32 nb, u32 pb,
+                                                int &hb, int &hmb) {
   if (__any(na | nb)) {
-    if (na) ha = hamming(ix.genome, sc.qpk, sc.nwords, pa);
-    if (nb) hb = hamming(ix.genome, sc.qpk, sc.nwords, pb);
+    if (na) ha = hamming(ix.genome, sc.qpk, sc.nwords, pa, hma);
+    if (nb) hb = hamming(ix.genome, sc.qpk, sc.nwords, pb, hmb);
   }
 }
 
@@ -994,21 +997,31 @@ __device__ __forceinline__ FilterStep filter_step_records(const DevIndex &ix, co
   const u32 ia = g0 + (sa >> 1), ib = g0 + (sb >> 1);
   // record start (in 16-byte blocks) and the bit of the record the window begins at
   const u32 ra = (ea + ((sa & 1u) ? sc.rec3 : 0u)) * ix.wrec_blocks, rb = (eb + ((sb & 1u) ? sc.rec3 : 0u)) * ix.wrec_blocks;
+  // A genome with IUPAC letters (uniform; no other genome takes this branch): such a letter can match where its arbitrary
+  // plane code does not, so the planes' distance is no lower bound there and the cutoff test below may not drop a
+  // candidate whose stretch holds one.  The record's own flag says so without the position: one 8-byte load per
+  // candidate, from the last block of a record whose lines the window's loads ask for anyway.
+  u32 fa = 0, fb = 0;
+  if (ix.multibit) {
+    if (va) fa = static_cast<u32>(ix.wrec[2 * (static_cast<u64>(ra) + ix.wrec_blocks - 1)] >> 63);
+    if (two && vb) fb = static_cast<u32>(ix.wrec[2 * (static_cast<u64>(rb) + ix.wrec_blocks - 1)] >> 63);
+  }
   int ha, hb = 0x7fff;
   if (lds.G == 2)
     hamming_records_lane<false>(ix, sc.qmask, sc.L, ra, ix.wrec_back - ia, va, rb, ix.wrec_back - ib, vb, two, ha, hb);
   else
     hamming_records_lane<true>(ix, sc.qmask, sc.L, ra, ix.wrec_back - ia, va, rb, ix.wrec_back - ib, vb, two, ha, hb);
   // the candidates that may still enter the set: these alone need their position
-  const bool ca = va && ha <= S.cutoff, cb = two && vb && hb <= S.cutoff;
+  const bool ca = va && (ha <= S.cutoff || fa), cb = two && vb && (hb <= S.cutoff || fb);
   u32 pa = 0, pb = 0;
+  int hma = ha, hmb = hb;
   if (__any(ca || cb)) {
     if (ca) pa = ((sa & 1u) ? sc.idx3[ea] : ix.index[ea]) - ia;
     if (cb) pb = ((sb & 1u) ? sc.idx3[eb] : ix.index[eb]) - ib;
-    const u32 na = ca ? n_within_reach(ix.nmap, pa) : 0u, nb = cb ? n_within_reach(ix.nmap, pb) : 0u;
-    redo_on_nibbles(ix, sc, na, pa, ha, nb, pb, hb);
+    const u32 na = ca ? (n_within_reach(ix.nmap, pa) | fa) : 0u, nb = cb ? (n_within_reach(ix.nmap, pb) | fb) : 0u;
+    redo_on_nibbles(ix, sc, na, pa, ha, hma, nb, pb, hb, hmb);
   }
-  return {ca, cb, pa, pb, ha, ha, hb, hb, (va ? 1u : 0u) + (vb ? 1u : 0u), 0u};
+  return {ca, cb, pa, pb, ha, hma, hb, hmb, (va ? 1u : 0u) + (vb ? 1u : 0u), 0u};
 }
 
 // One step of the window loop: the step's candidates were located and their index entries requested a step ago
@@ -1028,15 +1041,15 @@ __device__ __forceinline__ FilterStep filter_step_windows(const DevIndex &ix, co
   const PosCacheEntry ca = {va ? *slot_a : 0ull}, cb = {vb ? *slot_b : 0ull};
   const bool hit_a = va && ca.matches(pa), hit_b = vb && cb.matches(pb);
   int ha, hma, hb = 0x7fff, hmb = 0x7fff;
-  if constexpr (COOP) {  // (distances are complete sums: no genome letter here makes a word's share negative)
+  if constexpr (COOP) {  // (distances are complete sums: no genome letter the planes answer for makes a word's share negative)
     // (is an N within reach of the window?  asked before the windows so that the answers arrive with them)
     const u32 na = va && !hit_a ? n_within_reach(ix.nmap, pa) : 0u, nb = vb && !hit_b ? n_within_reach(ix.nmap, pb) : 0u;
     if (lds.G == 2)
       hamming_planes_pairs(ix, lds, sc.qmask, sc.L, pa, va && !hit_a, pb, vb && !hit_b, ha, hb);
     else
       hamming_planes(ix, lds, sc.qmask, sc.L, pa, va && !hit_a, pb, vb && !hit_b, ha, hb);
-    redo_on_nibbles(ix, sc, na, pa, ha, nb, pb, hb);
     hma = ha; hmb = hb;
+    redo_on_nibbles(ix, sc, na, pa, ha, hma, nb, pb, hb, hmb);
   }
   else
     hamming2(ix.genome, sc.qpk, sc.nwords, pa, va && !hit_a, pb, vb && !hit_b, ha, hma, hb, hmb);

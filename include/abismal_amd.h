@@ -105,6 +105,17 @@ int abm_index_set_seed_extension_cap(abm_index *ix, int letters2, int letters3);
  * longest read the context's records serve (0: none were built -- no planes, or not enough free device memory). */
 int abm_index_set_window_records(abm_index *ix, int max_read_len);
 uint32_t abm_ctx_window_records(const abm_ctx *ctx);
+/* Bit planes for genomes with IUPAC letters (no reference counterpart; results are unaffected).  One ambiguity letter
+ * (R, Y, M, K, S, W, B, D, H, V: a genome nibble with two or more bits) otherwise takes the whole device off the bit
+ * planes -- and with them off the window records, direct narrowing and device-written records: every launch then is the
+ * nibble build.  on != 0: the genome keeps its planes, and such letters are marked as blank nibbles (N) are -- in the
+ * planes' map of 4096-base chunks and in the window records' flags -- so that only the windows and probes within reach
+ * of one go back to the nibble array.  No seed-extension tables for such genomes either way.  On a genome without such
+ * letters the option changes nothing.  Default 0; must precede the first abm_ctx_create on the index.
+ * abm_ctx_plane_chunks: the chunks of the context's genome and how many of them are marked (blanks and IUPAC letters
+ * together): the share of the genome that goes the slow way.  0 and 0 when the context has no planes. */
+int abm_index_set_iupac_planes(abm_index *ix, int on);
+int abm_ctx_plane_chunks(const abm_ctx *ctx, uint64_t *chunks, uint64_t *flagged);
 /* the max_candidates (-c, src/abismal.cpp:2329) the calls on this index will pass, when it is not the value stored
  * in the index file: the tables of contexts created afterwards are built for it (0 = the file's value) */
 int abm_index_set_max_candidates(abm_index *ix, uint32_t max_candidates);
