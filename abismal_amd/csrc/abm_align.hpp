@@ -112,7 +112,9 @@ __device__ __forceinline__ void wavefront(const WaveLds &lds, const AlnJob &job,
 // a read with one mismatch gets).  Cells left of the read (q < 0) compute to 0 like the reference's zero-filled
 // table, cells right of it (q >= L) cannot reach a valid cell through from_left and are masked when published.
 // Arrows as the reference decides them: left wins ties, then above, then the diagonal.  Same table, scores, first
-// maximum per column as wavefront<TB>; 32-bit scores (the long-read kernel keeps wavefront<TB, true>).
+// maximum per column as wavefront<TB>; 32-bit scores (the long-read kernel keeps wavefront<TB, true>).  (Same table
+// wherever wavefront<TB> writes one: cells outside the read that no step of its schedule falls on -- 2 i + j below
+// bw - 1 or above 2 (L - 1 + bw) -- it leaves as they were, and no walk reads them; this run writes 3 there.)
 #ifndef ABM_TB_ROWS
 #define ABM_TB_ROWS true  // (false: the traceback run on the anti-diagonal schedule, for same-box comparisons)
 #endif
@@ -166,7 +168,8 @@ __device__ __forceinline__ void wavefront_rows(const WaveLds &lds, const AlnJob 
 }
 
 // where CIGARs go: fixed slots of `stride` ops per read; one with more ops goes whole into the launch's
-// overflow arena (bump-allocated), its slot's first word = where, and its count (> stride) says so
+// overflow arena (bump-allocated), its slot's first word = where, and its count (> stride) says so.  Without room
+// there the launch is flagged and the slot holds the CIGAR's first `stride` ops (of the ops the walk could keep).
 struct CigarSink {
   u32 stride;
   u32 ctmp_cap;        // entries of the reversed-ops scratch in LDS (longest read + 2: no CIGAR has more ops)
@@ -228,7 +231,7 @@ __device__ __forceinline__ void cigar_publish(const u32 *ctmp, const CigarWalk &
   // final order: [head clip] reversed(ops) [tail clip]
   const u32 full = n + (clip_head > 0) + (clip_tail > 0);  // the CIGAR's op count
   u32 *dst = cig_out;
-  u32 body = n, total = full;
+  u32 body = n, total = full, kept = n;  // kept: the ops the walk left in ctmp (ctmp[kept - 1] is the CIGAR's first)
   if (full > sink.stride) {  // too long for the slot: the whole CIGAR goes to the arena
     u32 at = 0xFFFFFFFFu;
     if (sink.arena != nullptr && n <= sink.ctmp_cap) {
@@ -240,9 +243,10 @@ __device__ __forceinline__ void cigar_publish(const u32 *ctmp, const CigarWalk &
       dst = sink.arena + at;
       if (lane == 0) store_out(cig_out, at);
     }
-    else {  // no room: the slot gets what fits and the launch is flagged
+    else {  // no room: the slot gets what fits -- the CIGAR's leading ops -- and the launch is flagged
       overflow = true;
-      body = min(min(n, sink.ctmp_cap), sink.stride);
+      kept = min(n, sink.ctmp_cap);
+      body = min(kept, sink.stride);
       total = min(body + (clip_head > 0) + (clip_tail > 0), sink.stride);
     }
   }
@@ -250,7 +254,7 @@ __device__ __forceinline__ void cigar_publish(const u32 *ctmp, const CigarWalk &
     u32 v;
     const u32 kk = k - (clip_head > 0 ? 1u : 0u);
     if (clip_head > 0 && k == 0) v = (static_cast<u32>(clip_head) << 4) | 4u;
-    else if (kk < body) v = ctmp[body - 1 - kk];
+    else if (kk < body) v = ctmp[kept - 1 - kk];
     else v = (static_cast<u32>(clip_tail) << 4) | 4u;
     store_out(dst + k, v);
     if (sink.fin && k < kSeCap) sink.fin[k] = v;

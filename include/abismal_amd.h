@@ -253,7 +253,8 @@ int abm_ctx_set_record_format(abm_ctx *ctx, int format);
  * says so) lies whole in the context's arena instead, beginning at the index its
  * slot's first word holds; abm_ctx_long_cigars() returns the arena of the last
  * call.  ABM_STATUS_CIGAR_OVERFLOW is only set if the arena itself ran out (one op
- * per read by default), in which case such slots hold what fitted.  d_status (one
+ * per read by default), in which case such slots hold what fitted: the CIGAR's first
+ * cig_stride ops.  d_status (one
  * uint32) is OR-ed with ABM_STATUS_* bits. max_len = longest read in the batch.
  * A context owns ONE set of workspaces: a device call first makes `stream` wait
  * for the context's previous device call (on whatever stream that ran), so calls

@@ -9,6 +9,7 @@
 // A job is (position, d): d only sets the band and picks the pilot, as in the kernel, so a set may state it freely.
 // Prints "OK <n sets> ..." or the first mismatch.
 #include "../../abismal_amd/csrc/abm_kernels.hip"
+#include "align_host.hpp"
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -57,116 +58,8 @@ __global__ __launch_bounds__(64) void run(const u64 *genome, const u64 *reads, c
   if (lane == 0) { out[blockIdx.x].best = best; out[blockIdx.x].n_ops = overflow ? 0xFFFFFFFFu : n_ops; }
 }
 
-// ---- the host's side -------------------------------------------------------------------------------------------
-static unsigned long long rng_state = 88172645463325252ull;
-static unsigned rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return static_cast<unsigned>(rng_state >> 16); }
-static int rnd_in(int lo, int hi) { return lo + static_cast<int>(rnd() % static_cast<unsigned>(hi - lo + 1)); }
-
-static std::vector<unsigned char> G;  // genome nibbles
-static int host_band(int d, int md) { const int v = 2 * std::min(d, md) + 1; return v < 0 ? 61 : std::min(61, v); }
-
-struct Aligned { int score; std::vector<u32> cigar; u32 pos; u32 alen; int ins, del; };
-// the reference's banded local alignment of read q[0, L) at position pos with band bw: scores 2 / -3 / -4, the first
-// maximum in row-major order, arrows with left before above before the diagonal
-static Aligned host_align(const unsigned char *q, int L, u32 pos, int bw, bool trace) {
-  const int rows = L + bw;
-  const u32 t_beg = pos - static_cast<u32>((bw - 1) / 2);
-  std::vector<int> C(static_cast<size_t>(rows) * bw, 0);
-  std::vector<unsigned char> T(static_cast<size_t>(rows) * bw, 3);
-  int best = 0, br = 0, bc = 0;
-  for (int i = 1; i < rows; ++i)
-    for (int j = 0; j < bw; ++j) {
-      const int r = i + j - bw;
-      if (r < 0 || r >= L) continue;
-      const bool match = (q[r] & G[t_beg + i - 1]) != 0;
-      const int sdiag = C[(i - 1) * bw + j] + (match ? 2 : -3);
-      int c = std::max(sdiag, 0), arrow = c == sdiag ? 0 : 3;
-      if (j < bw - 1 && r < L - 1) { const int up = C[(i - 1) * bw + j + 1] - 4; c = std::max(c, up); if (c == up) arrow = 2; }
-      if (j > 0) { const int left = C[i * bw + j - 1] - 4; c = std::max(c, left); if (c == left) arrow = 1; }
-      C[i * bw + j] = c;
-      T[i * bw + j] = static_cast<unsigned char>(arrow | (c > 0 ? 4 : 0));
-      if (c > best) { best = c; br = i; bc = j; }
-    }
-  Aligned a{best, {}, pos, static_cast<u32>(L), 0, 0};
-  if (!trace || best == 0) { a.cigar.push_back(static_cast<u32>(L) << 4); return a; }
-  int r = br, c = bc;
-  const int clip_tail = (L + bw - 1) - (r + c);
-  std::vector<u32> ops;
-  auto emit = [&](u32 run, int op) {
-    ops.push_back((run << 4) | static_cast<u32>(op));
-    if (op == 1) a.ins = static_cast<short>(a.ins + static_cast<unsigned char>(run));
-    if (op == 2) a.del = static_cast<short>(a.del + static_cast<unsigned char>(run));
-  };
-  auto step = [&](int ar) { if (ar != 1) --r; if (ar == 1) --c; if (ar == 2) ++c; };
-  int op = T[r * bw + c] & 3;
-  step(op);
-  u32 run = 1;
-  for (;;) {
-    const int cell = T[r * bw + c];
-    if (!(cell & 4)) break;
-    const int ar = cell & 3;
-    step(ar);
-    if (ar != op) { emit(run, op); run = 0; }
-    ++run;
-    op = ar;
-  }
-  emit(run, op);
-  const int clip_head = (r + c) - (bw - 1);
-  if (clip_head > 0) a.cigar.push_back((static_cast<u32>(clip_head) << 4) | 4u);
-  a.cigar.insert(a.cigar.end(), ops.rbegin(), ops.rend());
-  if (clip_tail > 0) a.cigar.push_back((static_cast<u32>(clip_tail) << 4) | 4u);
-  a.alen = static_cast<u32>(L - clip_tail - clip_head);
-  a.pos = pos - static_cast<u32>((bw - 1) / 2) + static_cast<u32>(r);
-  return a;
-}
-static int host_nm(int scr, u32 len, int ins, int del) {  // simple_aln::edit_distance, src/AbismalAlign.hpp:73-89
-  if (scr == 0) return static_cast<short>(len);
-  const int A = static_cast<short>(scr + 4 * (ins + del));
-  const u32 num = 2u * (len - static_cast<u32>(ins)) - static_cast<u32>(A);
-  return static_cast<short>(static_cast<short>(num / 5u) + ins + del);
-}
-
-struct Expect { u32 pos, flags; int diffs; std::vector<u32> cigar; };
-static Expect host_choose(const unsigned char *q, int L, std::vector<std::pair<u32, int>> jobs /* (pos, d) */) {
-  const int md = static_cast<short>(kFrac * L), invalid_at = static_cast<short>(0.4 * L), perfect = 2 * L;
-  std::sort(jobs.begin(), jobs.end());
-  int top = 0, b_d = 0;
-  u32 top_pos = 0, b_pos = 0, b_flags = 0;
-  for (const auto &j : jobs) {
-    if (j.second >= invalid_at) continue;
-    const int sc = host_align(q, L, j.first, host_band(j.second, md), false).score;
-    if (sc > top) { top = sc; top_pos = b_pos = j.first; b_d = j.second; b_flags = 0; }
-    else if (sc == top) {
-      const u32 gap = j.first > top_pos ? j.first - top_pos : top_pos - j.first;
-      if (sc == perfect ? j.first != top_pos : gap > 3u) b_flags |= kFlagAmbig;
-    }
-  }
-  Expect e{0, b_flags, 0x7fff, {}};
-  if (b_pos == 0) return e;
-  const Aligned a = host_align(q, L, b_pos, host_band(b_d, md), true);
-  const int nm = host_nm(top, a.alen, a.ins, a.del);
-  e.cigar = a.cigar;
-  if (a.alen >= std::max(32u, static_cast<u32>(0.6 * L)) && nm <= md) { e.diffs = nm; e.pos = a.pos; }
-  return e;
-}
-
-// plants a copy of the read at pos: `subs` substitutions, and from read index `gap_at` on (if > 0) the copy lacks
-// (gap < 0) or has in addition (gap > 0) |gap| bases, so that only a gapped alignment follows the read to its end
-static void plant(const unsigned char *q, int L, u32 pos, int subs, int gap_at, int gap, const std::vector<int> *sub_at = nullptr) {
-  std::vector<unsigned char> copy(q, q + L);
-  for (int k = 0; k < subs; ++k) {
-    const int at = sub_at ? (*sub_at)[k] : rnd_in(0, L - 1);
-    copy[at] = static_cast<unsigned char>(1u << ((__builtin_ctz(copy[at]) + 1 + (sub_at ? 0 : static_cast<int>(rnd() % 3))) & 3));
-  }
-  if (gap_at > 0 && gap < 0) copy.erase(copy.begin() + gap_at, copy.begin() + gap_at - gap);
-  if (gap_at > 0 && gap > 0) for (int k = 0; k < gap; ++k) copy.insert(copy.begin() + gap_at, static_cast<unsigned char>(1u << (rnd() & 3)));
-  for (size_t k = 0; k < copy.size(); ++k) G[pos + k] = copy[k];
-}
-static int hamming(const unsigned char *q, int L, u32 pos) {
-  int d = 0;
-  for (int k = 0; k < L; ++k) d += (q[k] & G[pos + k]) == 0;
-  return d;
-}
+// ---- the host's side: tests/hip/align_host.hpp (host_band, host_align, host_nm, host_choose, the genome nibbles G, plant, hamming)
+using namespace align_host;
 
 int main() {
   const int lens[3] = {50, 100, 150};
@@ -238,7 +131,7 @@ int main() {
     const int L = static_cast<int>(si.L), invalid_at = static_cast<short>(0.4 * L);
     std::vector<std::pair<u32, int>> jobs;
     for (u32 k = 0; k < si.n; ++k) jobs.push_back({si.pos[k], si.d[k]});
-    const Expect e = host_choose(q[s].data(), L, jobs);
+    const Expect e = host_choose(q[s].data(), L, jobs, kFrac);
     const SetOut &o = out[s];
     bool ok = o.best.pos == e.pos && o.best.flags == e.flags && o.best.diffs == e.diffs;
     if (ok && e.pos != 0) {
