@@ -13,5 +13,7 @@ from .api import (  # noqa: F401
     Inflater, bgzf_scan, BGZF_BLOCK_DTYPE, ERR_INFLATE,
     Deflater, deflate_bgzf_host, bgzf_deflate_bound, ERR_CAPACITY,
     INFLATE_OK, INFLATE_HEADER, INFLATE_DATA, INFLATE_SIZE, INFLATE_CRC,
+    FastqParser, FastqReads, fastq_parse_host, fastq_sizes, FASTQ_INFO_DTYPE, ERR_FASTQ,
+    FASTQ_OK, FASTQ_EMPTY_NAME, FASTQ_TOO_LONG, FASTQ_NO_BASE,
 )
 from .build import build  # noqa: F401

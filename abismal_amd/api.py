@@ -13,10 +13,13 @@ RECORDS_SAM, RECORDS_BAM = 0, 1
 INFLATE_OK, INFLATE_HEADER, INFLATE_DATA, INFLATE_SIZE, INFLATE_CRC = 0, 1, 2, 3, 4
 ERR_INFLATE = -3
 ERR_CAPACITY = -2
+FASTQ_OK, FASTQ_EMPTY_NAME, FASTQ_TOO_LONG, FASTQ_NO_BASE = 0, 1, 2, 3
+ERR_FASTQ = -4
 
 HIT_DTYPE = np.dtype([("diffs", "<i2"), ("flags", "<u2"), ("pos", "<u4")])
 PAIR_DTYPE = np.dtype([("aln_score", "<i2"), ("reserved", "<i2"), ("r1", HIT_DTYPE), ("r2", HIT_DTYPE)])
 BGZF_BLOCK_DTYPE = np.dtype([("at", "<u8"), ("text_at", "<u8"), ("len", "<u4"), ("text_len", "<u4")])  # abm_bgzf_block
+FASTQ_INFO_DTYPE = np.dtype([("n_records", "<u8"), ("blob_bytes", "<u8"), ("max_len", "<u4"), ("code", "<u4"), ("line", "<u8"), ("value", "<u8")])  # abm_fastq_info
 
 EXPORTED_SYMBOLS = [
     "abm_last_error", "abm_default_params", "abm_index_open", "abm_index_close",
@@ -30,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "abm_index_set_iupac_planes", "abm_ctx_plane_chunks",
     "abm_bgzf_scan", "abm_inflater_create", "abm_inflater_destroy", "abm_inflate_bgzf", "abm_inflate_bgzf_device",
     "abm_deflate_bgzf_bound", "abm_deflater_create", "abm_deflater_destroy", "abm_deflate_bgzf", "abm_deflate_bgzf_device", "abm_deflate_bgzf_host",
+    "abm_fastq_sizes", "abm_fastq_parser_create", "abm_fastq_parser_destroy", "abm_fastq_parse", "abm_fastq_parse_device", "abm_fastq_parse_host",
 ]
 
 
@@ -144,6 +148,14 @@ def load_library():
         lib.abm_deflate_bgzf.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, u64p, vp, C.c_uint64, u64p]
         lib.abm_deflate_bgzf_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, vp, vp, vp]
         lib.abm_deflate_bgzf_host.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, u64p, vp, C.c_uint64, u64p]
+    if hasattr(lib, "abm_fastq_parse"):
+        lib.abm_fastq_sizes.argtypes = [vp, vp, vp]
+        lib.abm_fastq_sizes.restype = None
+        lib.abm_fastq_parser_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        lib.abm_fastq_parser_destroy.argtypes = [vp]
+        lib.abm_fastq_parse.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp]
+        lib.abm_fastq_parse_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, vp]
+        lib.abm_fastq_parse_host.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp]
     _lib = lib
     return lib
 
@@ -295,6 +307,87 @@ class Deflater:
     def deflate_device(self, d_text, text_bytes, block_bytes, d_out, out_capacity, d_out_bytes, d_blocks, stream=0):
         """abm_deflate_bgzf_device: all d_* are integer device addresses (e.g. tensor.data_ptr()); not synchronised"""
         _check(self._lib.abm_deflate_bgzf_device(self.handle, d_text, text_bytes, block_bytes, d_out, out_capacity, d_out_bytes, d_blocks, stream))
+
+
+def fastq_sizes():
+    """abm_fastq_sizes: (bytes of text per tile, tile counts per step of the one-workgroup scans, records per chunk)"""
+    a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    load_library().abm_fastq_sizes(C.byref(a), C.byref(b), C.byref(c))
+    return int(a.value), int(b.value), int(c.value)
+
+
+# what the parsers return: blob (bytes), off (u64[n + 1]), name_at (u64[n]), name_len (u32[n]), info (a dict of
+# abm_fastq_info's fields); with info["code"] != 0 the arrays hold unspecified values
+FastqReads = collections.namedtuple("FastqReads", "blob off name_at name_len info")
+
+
+def _fastq_info(raw):
+    return {k: int(raw[k][0]) for k in FASTQ_INFO_DTYPE.names}
+
+
+def _fastq_call(call, data, min_letters):
+    """one of abm_fastq_parse / abm_fastq_parse_host (the parser already bound) over `data` -> FastqReads; the buffers
+    are sized by a first call without any"""
+    buf = np.frombuffer(data, dtype=np.uint8)
+    text = buf.ctypes.data if len(buf) else None
+    info = np.zeros(1, dtype=FASTQ_INFO_DTYPE)
+    off = np.zeros(1, dtype=np.uint64)
+    rc = call(text, len(buf), int(min_letters), None, 0, off.ctypes.data, None, None, 0, info.ctypes.data)
+    if rc not in (0, ERR_FASTQ, ERR_CAPACITY):
+        _check(rc)
+    n, m = int(info["n_records"][0]), int(info["blob_bytes"][0])
+    blob = np.zeros(max(1, m), dtype=np.uint8)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    name_at = np.zeros(max(1, n), dtype=np.uint64)
+    name_len = np.zeros(max(1, n), dtype=np.uint32)
+    rc = call(text, len(buf), int(min_letters), blob.ctypes.data, m, off.ctypes.data, name_at.ctypes.data, name_len.ctypes.data, n, info.ctypes.data)
+    if rc not in (0, ERR_FASTQ):
+        _check(rc)
+    return FastqReads(blob[:m].tobytes(), off, name_at[:n], name_len[:n], _fastq_info(info))
+
+
+def fastq_parse_host(data, min_letters=44):
+    """abm_fastq_parse_host: FASTQ text (bytes) as reads, with ReadLoader's rules, serially on this thread -> FastqReads.
+    An error in the text shows in info["code"] / ["line"] / ["value"] (ABM_ERR_FASTQ does not raise), any other failure
+    raises."""
+    return _fastq_call(load_library().abm_fastq_parse_host, data, min_letters)
+
+
+class FastqParser:
+    """abm_fastq_parser_create / abm_fastq_parser_destroy + abm_fastq_parse: FASTQ text parsed on the device"""
+
+    def __init__(self, device=0):
+        self._lib = load_library()
+        h = C.c_void_p()
+        _check(self._lib.abm_fastq_parser_create(int(device), C.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if self.handle:
+            self._lib.abm_fastq_parser_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def parse(self, data, min_letters=44):
+        """abm_fastq_parse over `data` (bytes) -> FastqReads; the same bytes as fastq_parse_host gives"""
+        return _fastq_call(lambda *a: self._lib.abm_fastq_parse(self.handle, *a), data, min_letters)
+
+    def parse_device(self, d_text, text_bytes, min_letters, d_blob, blob_capacity, d_off, d_name_at, d_name_len, rec_capacity, d_info, stream=0):
+        """abm_fastq_parse_device: all d_* are integer device addresses (e.g. tensor.data_ptr()); d_name_at / d_name_len may
+        be None; d_info receives FASTQ_INFO_DTYPE; not synchronised"""
+        _check(self._lib.abm_fastq_parse_device(self.handle, d_text, text_bytes, int(min_letters), d_blob, blob_capacity, d_off, d_name_at, d_name_len,
+                                                rec_capacity, d_info, stream))
 
 
 # letters of the seed-extension tables that Index() asks for when its caller does not say: None = the library's

@@ -138,6 +138,7 @@ constexpr unsigned kPeDeviceSamWorkers = 0;
 // interleaved runs each: DESIGN.md 4.5); ABM_CLI_DEVICE_SAM=1 turns them on.
 constexpr unsigned kSeDeviceBamWorkers = 0, kPeDeviceBamWorkers = 0;
 std::atomic<uint64_t> g_inflate_device_blocks{0}, g_inflate_host_blocks{0}, g_inflate_fallback_blocks{0};  // BGZF blocks of the input by who inflated them (fallback: the device rejected it, the host did not)
+std::atomic<uint64_t> g_parse_device_slices{0}, g_parse_host_slices{0}, g_parse_fallback_slices{0};  // slices of the input by who parsed them (fallback: the device's call did not give a result -- an error in the text, a failure -- and the host parsed the slice again)
 std::atomic<uint64_t> g_deflate_device_blocks{0}, g_deflate_host_blocks{0}, g_deflate_fallback_blocks{0};  // BGZF blocks of -B output by who deflated them (fallback: the device call failed, the host redid its slice)
 std::atomic<uint64_t> g_device_records{0}, g_host_records{0};  // SAM / BAM records whose text the kernels / the formatters wrote
 
@@ -168,6 +169,7 @@ struct RunPlan {
   size_t reserve_reads = 0;
   bool stream_slices = false, device_sam = false;
   bool device_deflate = false;  // -B at -z 1: the workers deflate a slice's records on the run's GPUs (ABM_CLI_DEVICE_DEFLATE)
+  bool device_parse = false;    // the workers parse a slice's FASTQ text on the run's GPUs (ABM_CLI_DEVICE_PARSE)
   bool device_inflate = false;  // BGZF input: the workers inflate a chunk's blocks on the run's GPUs (ABM_CLI_DEVICE_INFLATE)
   int pe_text_per_gpu = 0;   // paired: contexts per GPU whose batches carry SAM text from the device
   int se_mode = 0, pe_mode = 0;
@@ -294,6 +296,10 @@ RunPlan make_plan(const Options &opt, const Topology &topo, const CpuQuota &quot
   // of them), =0 on the host; the host is the default.  Virtual GPUs have no device; other input ignores it.
   const char *where = std::getenv("ABM_CLI_DEVICE_INFLATE");
   p.device_inflate = where && where[0] == '1' && p.input == InputKind::Bgzf && !p.virtual_gpus;
+  // where FASTQ text becomes reads: ABM_CLI_DEVICE_PARSE=1 on the run's GPUs (every host worker has a parser on one of them),
+  // otherwise on the host; the host is the default.  Virtual GPUs have no device.
+  const char *parse_where = std::getenv("ABM_CLI_DEVICE_PARSE");
+  p.device_parse = parse_where && parse_where[0] == '1' && !p.virtual_gpus;
   // where -B output is deflated: ABM_CLI_DEVICE_DEFLATE=1 on the run's GPUs, dealt out as the inflaters are; the host is
   // the default.  It stands in for the fast encoder alone (-z 1): levels 0 and 2..9 keep their meaning, on the host.
   const char *deflate_where = std::getenv("ABM_CLI_DEVICE_DEFLATE");
@@ -624,6 +630,7 @@ struct Pipeline {
   std::vector<LineFile> lf;
   bool count_gated = false;  // BGZF: inflating further ahead is on hold until slices have been written
   std::vector<DeviceDeflate> deflaters;  // device deflate of -B output: likewise
+  std::vector<DeviceParse> parsers;      // device parse: likewise
   std::vector<DeviceBgzf> inflaters;  // device inflate: one per host worker, dealt round the run's GPUs; empty otherwise
   std::vector<std::unique_ptr<Batch>> live_batches;
   int mappers_live;
@@ -666,6 +673,10 @@ struct Pipeline {
     if (plan.device_inflate) {
       inflaters = std::vector<DeviceBgzf>(plan.n_host);
       for (unsigned t = 0; t < plan.n_host; ++t) inflaters[t].open(plan.dev_of[t % static_cast<unsigned>(plan.n_gpus)]);
+    }
+    if (plan.device_parse) {
+      parsers = std::vector<DeviceParse>(plan.n_host);
+      for (unsigned t = 0; t < plan.n_host; ++t) parsers[t].open(plan.dev_of[t % static_cast<unsigned>(plan.n_gpus)]);
     }
     if (plan.device_deflate) {
       deflaters = std::vector<DeviceDeflate>(plan.n_host);
@@ -1173,12 +1184,33 @@ struct Pipeline {
     wake_everyone();
   }
 
-  void parse_slice(std::unique_ptr<Slice> sl) {
+  // `dev`: the calling worker's parser (device parse), else null.  A slice the device gives no result for -- an error in
+  // its text, a failed call, ends of a pair that disagree -- is parsed again on the host, whose message or result stands.
+  void parse_slice(std::unique_ptr<Slice> sl, DeviceParse *dev) {
     const auto t0 = now();
     Region &R = regions[sl->region];
+    bool on_device = dev != nullptr;
+    for (int pass = 0; pass < 2; ++pass) {
+      parse_ends(*sl, on_device ? dev : nullptr, on_device);
+      if (!on_device || !(plan.paired && sl->names[0].size() != sl->names[1].size())) break;
+      on_device = false;  // (once more on the host, which then says so below)
+      ++g_parse_fallback_slices;
+    }
+    if (!dev) ++g_parse_host_slices;
+    else if (on_device) ++g_parse_device_slices;
+    finish_parsed(std::move(sl), R, t0);
+  }
+  // every end's text -> names, blob, off; on_device: cleared when an end had to be parsed on the host
+  void parse_ends(Slice &s, DeviceParse *dev, bool &on_device) {
+    Slice *sl = &s;
+    auto parse = [&](int e, const char *text, size_t n) {
+      if (dev && dev->run(text, n, sl->names[e], sl->blob[e], sl->off[e])) return;
+      if (dev && on_device) { on_device = false; ++g_parse_fallback_slices; }  // (counted here: parse_raw may end the run)
+      parse_raw(text, n, sl->first_line[e], opt.reads[e], sl->names[e], sl->blob[e], sl->off[e]);
+    };
     for (int e = 0; e < plan.ends; ++e) {
       if (plan.plain() && lf[e].map) {  // parsed in place: the names are views into the mapping
-        parse_raw(lf[e].map + sl->byte_lo[e], sl->byte_hi[e] - sl->byte_lo[e], sl->first_line[e], opt.reads[e], sl->names[e], sl->blob[e], sl->off[e]);
+        parse(e, lf[e].map + sl->byte_lo[e], sl->byte_hi[e] - sl->byte_lo[e]);
         continue;
       }
       if (plan.plain()) {
@@ -1188,8 +1220,10 @@ struct Pipeline {
         read_range(lf[e].fd, opt.reads[e], sl->raw[e].p, sl->byte_lo[e], sl->byte_hi[e]);
         sl->raw[e].n = len;
       }
-      parse_raw(sl->raw[e], sl->first_line[e], opt.reads[e], sl->names[e], sl->blob[e], sl->off[e]);
+      parse(e, sl->raw[e].p, sl->raw[e].n);
     }
+  }
+  void finish_parsed(std::unique_ptr<Slice> sl, Region &R, std::chrono::steady_clock::time_point t0) {
     if (plan.paired && sl->names[0].size() != sl->names[1].size())
       throw std::runtime_error("paired-end batch sizes differ. Batch 1: " + std::to_string(sl->names[0].size()) +
                                ", batch 2: " + std::to_string(sl->names[1].size()) +
@@ -1739,7 +1773,7 @@ struct Pipeline {
         }
         if (to_count) count_chunk(ce, ck, count_buf, inflaters.empty() ? nullptr : &inflaters[id]);
         else if (to_format) format_task(to_format, deflaters.empty() ? nullptr : &deflaters[id]);
-        else parse_slice(std::move(to_parse));
+        else parse_slice(std::move(to_parse), parsers.empty() ? nullptr : &parsers[id]);
       }
     }
     catch (...) { fail(); }
@@ -1901,6 +1935,18 @@ void write_stats_file(const Options &opt, const RunPlan &plan, const Stats3 &tot
   so.close();
   if (!so) throw std::runtime_error("failed writing stats file: " + opt.stats);
 }
+std::string parse_report(const RunPlan &plan) {
+  std::ostringstream os;
+  os << "{\"where\": \"" << (plan.device_parse ? "device" : "host") << "\", \"device_slices\": " << g_parse_device_slices.load() << ", \"host_slices\": " << g_parse_host_slices.load()
+     << ", \"fallback_slices\": " << g_parse_fallback_slices.load() << "}";
+  return os.str();
+}
+// a run that ended with an error still says who parsed its slices (a slice the device refused is how such a run ends)
+void write_failed_timing_file(const Options &opt, const RunPlan &plan) {
+  if (opt.timing.empty()) return;
+  std::ofstream tf(opt.timing);
+  tf << "{\"failed\": true, \"parse\": " << parse_report(plan) << "}\n";
+}
 void write_timing_file(const Options &opt, const RunPlan &plan, const Topology &topo, const CpuQuota &quota, const Pipeline &pl, const Report &rep,
                        const std::vector<abm_ctx *> &ctxs) {
   if (opt.timing.empty()) return;
@@ -1912,6 +1958,7 @@ void write_timing_file(const Options &opt, const RunPlan &plan, const Topology &
      << ", \"sam_text_by\": \"" << (plan.device_sam ? "device" : "host") << "\", \"sam_records\": {\"device\": " << g_device_records.load() << ", \"host\": " << g_host_records.load() << "}, \"pe_text_contexts_per_gpu\": " << (plan.paired && plan.device_sam ? plan.pe_text_per_gpu : 0) << ", \"window_records_serve_reads_up_to\": " << (ctxs.empty() ? 0u : abm_ctx_window_records(ctxs[0])) << ", \"plane_chunks\": " << plane_chunks << ", \"plane_chunks_flagged\": " << plane_flagged << ", \"host_threads\": " << plan.n_host << ", \"numa_nodes\": " << plan.n_nodes << ", \"pinned\": " << (topo.pinning ? "true" : "false")
      << ", \"out_parts\": " << plan.n_regions << ", \"out_bytes\": " << pl.out_bytes << ", \"batches\": " << pl.n_batches << ", \"max_lead_in_records\": " << pl.max_lead << ", \"region_lead_in_scanned_records\": " << pl.region_lead_scanned << ", \"region_lead_in_records\": " << pl.region_lead_records
      << ", \"inflate\": {\"where\": \"" << (plan.device_inflate ? "device" : "host") << "\", \"device_blocks\": " << g_inflate_device_blocks.load() << ", \"host_blocks\": " << g_inflate_host_blocks.load() << ", \"fallback_blocks\": " << g_inflate_fallback_blocks.load() << "}"
+     << ", \"parse\": " << parse_report(plan)
      << ", \"deflate\": {\"where\": \"" << (plan.device_deflate ? "device" : "host") << "\", \"device_blocks\": " << g_deflate_device_blocks.load() << ", \"host_blocks\": " << g_deflate_host_blocks.load() << ", \"fallback_blocks\": " << g_deflate_fallback_blocks.load() << "}"
      << ", \"batch_reads\": " << plan.batch_reads << ", \"host_ceiling\": " << (plan.virtual_gpus ? "true" : "false")
      << ", \"batches_per_gpu\": [";
@@ -1970,7 +2017,8 @@ int cmd_map(int argc, char **argv) {
   quota.throttled(throttled0, throttled_s0);
   Pipeline pl(plan, opt, topo, ch, ctxs, argc, argv);
   pl.prewarm();
-  pl.run();
+  try { pl.run(); }
+  catch (...) { write_failed_timing_file(opt, plan); throw; }
   quota.throttled(rep.throttled, rep.throttled_s);
   rep.throttled -= throttled0;
   rep.throttled_s -= throttled_s0;

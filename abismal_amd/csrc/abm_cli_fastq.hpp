@@ -3,6 +3,7 @@
 // tests/cpp/cli_parse_harness.cpp, which includes that): everything here has internal linkage.
 #pragma once
 #include "abm_cli_records.hpp"
+#include "abm_fastq_core.hpp"
 
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -14,7 +15,7 @@
 
 namespace {
 
-constexpr uint32_t kPadding = 32767;
+constexpr uint32_t kPadding = abm_fastq::kMaxRead;  // 32767
 uint32_t g_min_read_len = 44;  // key weight + the index's window - 1 (src/abismal.cpp:212-213): 36 with a short-read index
 uint32_t g_map_read_len = 35;  // shortest trimmed read the library maps (DevIndex::map_len, abm_device.hpp): 29 with a short-read index
 
@@ -329,6 +330,7 @@ struct RawSplitter {
   bool exhausted() const { return eof && carry.empty(); }
 };
 
+// (the per-record rules are abm_fastq_core.hpp's: the device parser and abm_fastq_parse_host apply the same)
 void parse_raw(const char *text, size_t text_n, uint64_t first_line, const std::string &path, std::vector<NameRef> &names,
                RawBuf &blob, std::vector<uint64_t> &off) {
   names.clear(); blob.clear(); off.assign(1, 0);
@@ -336,32 +338,23 @@ void parse_raw(const char *text, size_t text_n, uint64_t first_line, const std::
   names.reserve(text_n / 200 + 16);
   off.reserve(text_n / 200 + 16);
   const char *p = text, *end = p + text_n;
-  std::string line;
   for (uint64_t k = 0; p < end; ++k) {
     const char *nl = static_cast<const char *>(std::memchr(p, '\n', static_cast<size_t>(end - p)));
     const char *le = nl ? nl : end;
+    const size_t len = static_cast<size_t>(le - p);
     if (k % 4 == 0) {
-      if (le == p)
+      if (len == 0)
         throw std::runtime_error("file " + path + " contains an empty read name at line " + std::to_string(first_line + k));
-      const char *q = p + 1;
-      while (q < le && *q != ' ' && *q != '\t') ++q;
-      names.push_back(NameRef{p + 1, static_cast<uint32_t>(q - (p + 1))});
+      names.push_back(NameRef{p + 1, abm_fastq::name_length(reinterpret_cast<const uint8_t *>(p), len)});
     }
     else if (k % 4 == 1) {
-      const size_t len = static_cast<size_t>(le - p);
-      if (len >= kPadding)
+      if (abm_fastq::too_long(len))
         throw std::runtime_error("found a read of size " + std::to_string(len) +
                                  ", which is too long. Maximum allowed read size = " + std::to_string(kPadding));
-      size_t informative = 0;
-      for (const char *c = p; c < le; ++c) informative += (*c != 'N');
-      if (informative >= g_min_read_len) {
-        const char *e = le;
-        while (e > p && e[-1] == 'N') --e;                       // remove Ns from 3'
-        const char *b = p;
-        while (b < e && *b != 'A' && *b != 'C' && *b != 'G' && *b != 'T') ++b;  // ... and everything before the first base
-        if (b == e) throw std::runtime_error("read without A/C/G/T at line " + std::to_string(first_line + k));
-        blob.append(b, static_cast<size_t>(e - b));
-      }
+      uint32_t at = 0, n = 0;
+      if (abm_fastq::seq_rules(reinterpret_cast<const uint8_t *>(p), static_cast<uint32_t>(len), g_min_read_len, at, n) == ABM_FASTQ_NO_BASE)
+        throw std::runtime_error("read without A/C/G/T at line " + std::to_string(first_line + k));
+      blob.append(p + at, n);
       off.push_back(blob.size());
     }
     if (!nl) break;

@@ -215,6 +215,43 @@ struct DeviceDeflate {
   }
 };
 
+// one thread's FASTQ parser on a GPU (the C ABI's abm_fastq_parser: its own stream, device buffers and pinned staging), with
+// the name table of its current call
+struct DeviceParse {
+  abm_fastq_parser *par = nullptr;
+  std::vector<uint64_t> name_at;
+  std::vector<uint32_t> name_len;
+  DeviceParse() = default;
+  DeviceParse(const DeviceParse &) = delete;
+  ~DeviceParse() { if (par) abm_fastq_parser_destroy(par); }
+  void open(int device) {
+    if (!par && abm_fastq_parser_create(device, &par) != 0) throw std::runtime_error(abm_last_error());
+  }
+  // text -> names (views into it), blob, off, as parse_raw leaves them.  false: the text has an error or the call failed
+  // (the caller parses it on the host, which throws the reference's message or gives its result).  The capacities start
+  // from what records look like and follow the call's own figures when it says they were too small.
+  bool run(const char *text, size_t text_n, std::vector<NameRef> &names, RawBuf &blob, std::vector<uint64_t> &off) {
+    uint64_t recs = text_n / 64 + 16, bytes = text_n / 2 + 64;
+    abm_fastq_info info;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      blob.clear();
+      blob.reserve(bytes);
+      off.resize(recs + 1);
+      name_at.resize(recs);
+      name_len.resize(recs);
+      const int rc = abm_fastq_parse(par, text, text_n, g_min_read_len, blob.p, bytes, off.data(), name_at.data(), name_len.data(), recs, &info);
+      if (rc == ABM_ERR_CAPACITY && attempt == 0) { recs = info.n_records; bytes = info.blob_bytes; continue; }
+      if (rc != 0) return false;
+      blob.n = info.blob_bytes;
+      off.resize(info.n_records + 1);
+      names.resize(info.n_records);
+      for (uint64_t j = 0; j < info.n_records; ++j) names[j] = NameRef{text + name_at[j], name_len[j]};
+      return true;
+    }
+    return false;
+  }
+};
+
 // a mapped input file that shrinks under the run (truncated, a network file system losing it) faults with SIGBUS
 void install_sigbus_handler() {
   struct sigaction sa;

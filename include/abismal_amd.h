@@ -474,6 +474,69 @@ int abm_deflate_bgzf_host(const void *text, uint64_t text_bytes, uint32_t block_
                           void *out, uint64_t out_capacity, uint64_t *out_bytes,
                           abm_bgzf_block *blocks, uint64_t blocks_capacity, uint64_t *n_blocks);
 
+/* FASTQ text parsed on the device: what ReadLoader does to every record on the host (src/abismal.cpp:164-201), for a whole
+ * text at once, so that text inflated in HBM becomes the seq_blob / seq_off of abm_map_se_device / abm_map_pe_device
+ * without leaving it.  The rules (abm_fastq_core.hpp has them once, for the CLI's host parser, the kernels and
+ * abm_fastq_parse_host alike):
+ *   lines     only '\n' ends a line; a last line without one counts.  The text begins at a record's first line; line k
+ *             belongs to record k / 4, and L lines are (L + 2) / 4 records: a trailing name line without its sequence line
+ *             is not a record.  Lines 4j + 2 and 4j + 3 are never looked at.
+ *   name      line 4j: the bytes after its first byte up to the first space, tab or end of line; an empty line is
+ *             ABM_FASTQ_EMPTY_NAME
+ *   sequence  line 4j + 1: 32767 bytes or more are ABM_FASTQ_TOO_LONG; with fewer than min_letters bytes that are not 'N'
+ *             (44, or 36 with a short-read index) the read is empty; otherwise trailing 'N's are dropped, then everything
+ *             before the first A, C, G or T; nothing left is ABM_FASTQ_NO_BASE
+ *   errors    of several, the one on the lowest line is the call's, as the host throws at the first
+ * The kernels: newlines counted per tile of ABM_FASTQ_TILE_BYTES, the counts scanned by one workgroup
+ * ABM_FASTQ_SCAN_TILES at a time, every newline ranked into its record's line ends, a group of 16 lanes per record for
+ * the name's length and the read's range, the read lengths summed and scanned per chunk of ABM_FASTQ_CHUNK_RECORDS, the
+ * reads copied.  The outputs are a function of the text and min_letters alone. */
+typedef struct abm_fastq_parser abm_fastq_parser; /* one stream on one GPU + its grow-only device buffers and pinned staging */
+enum { ABM_FASTQ_OK = 0, ABM_FASTQ_EMPTY_NAME, ABM_FASTQ_TOO_LONG, ABM_FASTQ_NO_BASE };
+#define ABM_ERR_FASTQ (-4)
+#define ABM_FASTQ_TILE_BYTES 4096
+#define ABM_FASTQ_SCAN_TILES 1024
+#define ABM_FASTQ_CHUNK_RECORDS 1024
+/* n_records: the text's records; blob_bytes: the reads' bytes; max_len: the longest read after trimming; code: ABM_FASTQ_*;
+ * line: the error's line, 0-based within the call's text; value: the line's length for ABM_FASTQ_TOO_LONG, else 0.  A
+ * record whose sequence line is an error counts as an empty read. */
+typedef struct { uint64_t n_records, blob_bytes; uint32_t max_len, code; uint64_t line, value; } abm_fastq_info;
+/* the three sizes above as the library was built with them (tests place their texts' edges by them) */
+void abm_fastq_sizes(uint32_t *tile_bytes, uint32_t *scan_tiles, uint32_t *chunk_records);
+/* A parser is independent of any abm_ctx, inflater and deflater; several on one device run side by side, each on its own
+ * stream.  Calls on one parser are serialised.  Without a HIP device the call fails with a message
+ * (abm_fastq_parse_host needs none). */
+int abm_fastq_parser_create(int device, abm_fastq_parser **out);
+void abm_fastq_parser_destroy(abm_fastq_parser *p);
+/* Host buffers (pageable is fine): upload, parse, copy out; returns when the outputs are written.  off receives
+ * n_records + 1 offsets into blob, the first 0 -- what abm_map_se_batch takes as seq_off -- and so holds rec_capacity + 1
+ * entries; name_at[j] is the offset in `text` of record j's first name byte and name_len[j] the name's length (either may
+ * be NULL; rec_capacity entries).  *info is written by every call that gets as far as looking at the text.
+ *   0                 done
+ *   ABM_ERR_FASTQ     the call ran and info->code != 0: info says which line; n_records is still the text's, the outputs
+ *                     hold unspecified bytes inside their ranges
+ *   ABM_ERR_CAPACITY  n_records > rec_capacity or blob_bytes > blob_capacity: info says what is needed (an error in the
+ *                     text included), nothing else was written
+ *   other < 0         the call itself failed (abm_last_error()): a null pointer or a text of 2^32 bytes or more (checked
+ *                     before anything is launched), a HIP error.  Nothing was written. */
+int abm_fastq_parse(abm_fastq_parser *p, const void *text, uint64_t text_bytes, uint32_t min_letters,
+                    char *blob, uint64_t blob_capacity, uint64_t *off, uint64_t *name_at, uint32_t *name_len,
+                    uint64_t rec_capacity, abm_fastq_info *info);
+/* The same with everything resident in HBM (d_* are device pointers, d_text at any byte alignment), enqueued on `stream`
+ * (a hipStream_t; NULL = default stream) and not synchronised, as abm_inflate_bgzf_device: returns 0 once enqueued, the
+ * outcome is *d_info.  If d_info->n_records > rec_capacity nothing else was written and the other fields of *d_info are 0;
+ * otherwise *d_info is complete and d_off, d_name_at, d_name_len are written; bytes of the reads at or beyond
+ * d_blob + blob_capacity are left out (blob_bytes says whether there were any).  The line ends and read lengths are kept in
+ * the parser's own scratch memory, which a later call on the same parser reuses: order such calls on one stream. */
+int abm_fastq_parse_device(abm_fastq_parser *p, const void *d_text, uint64_t text_bytes, uint32_t min_letters,
+                           char *d_blob, uint64_t blob_capacity, uint64_t *d_off, uint64_t *d_name_at,
+                           uint32_t *d_name_len, uint64_t rec_capacity, abm_fastq_info *d_info, void *stream);
+/* The same rules run serially on the calling thread, no device needed: the specification of the device's bytes.
+ * Arguments and results as abm_fastq_parse. */
+int abm_fastq_parse_host(const void *text, uint64_t text_bytes, uint32_t min_letters,
+                         char *blob, uint64_t blob_capacity, uint64_t *off, uint64_t *name_at, uint32_t *name_len,
+                         uint64_t rec_capacity, abm_fastq_info *info);
+
 #ifdef __cplusplus
 }
 #endif
